@@ -29,6 +29,7 @@ import argparse
 import json
 import os
 import platform
+import signal
 import socket
 import subprocess
 import sys
@@ -44,6 +45,8 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); 6290 GB/s is the measured copy ceiling
 IN_W, IN_H, OUT_W, OUT_H = 1280, 1024, 640, 480
 SEQ50K = 50000
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files of all ranks together stay under 64 MB
+DUMP_SEED = 20240611
 
 
 def _flush_c_stdio():
@@ -115,6 +118,11 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU time of the all-core baseline sample")
     p.add_argument("--dump-dir", default="", help="test hook: every rank writes its first --dump-frames outputs here")
     p.add_argument("--dump-frames", type=int, default=0)
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the headline's timed steps, write what its last timed step computed: every output array of the launch for a "
+                        "fixed, seeded sample of its frames (their global indices in DIR/frames.npy, float64), at most 64 MB in all.  "
+                        "DIR/<name>.npy (float32) holds finite numbers only: 0 where the caller receives NaN (an overexposed pixel) or inf, "
+                        "and DIR/<name>_nonfinite.npy (float32) says which (0 finite, 1 NaN, 2 +inf, 3 -inf) -- compare the two together")
     return p.parse_args()
 
 
@@ -342,16 +350,31 @@ def launch_ranks_if_needed(args):
     if args.gpus <= 1:
         return
     backend = os.environ.get("MDC_BENCH_BACKEND", "nccl")
-    ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    # the devices are counted by a short-lived child: this process never opens the GPU, so `--gpus N` holds N processes on it (the
+    # ranks), not N + 1
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                           stdout=subprocess.PIPE, text=True, timeout=300)
+    if probe.returncode != 0:
+        raise SystemExit("bench.py: counting the visible GPUs failed (exit status %d)" % probe.returncode)
+    ndev = int(probe.stdout.split()[-1])
     if ndev < args.gpus and backend != "gloo":
         raise SystemExit("bench.py: --gpus %d but %d GPU(s) visible; one rank per GPU over RCCL needs %d devices "
                          "(MDC_BENCH_BACKEND=gloo shares devices between ranks, for tests only)" % (args.gpus, ndev, args.gpus))
     if ndev < 1:
         raise SystemExit("bench.py needs a GPU (there is no CPU fallback for the hot path)")
+    # the ranks run under a child launcher, and this process passes its signals on and returns the launcher's exit status
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    child = subprocess.Popen(cmd)
+
+    def forward(signum, _frame):  # a time limit on this process reaches the launcher (which stops its ranks)
+        child.send_signal(signum)
+
+    for s in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
+        signal.signal(s, forward)
+    rc = child.wait()
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 class Dist:
@@ -712,6 +735,36 @@ class Workload:
         np.save(os.path.join(args.dump_dir, "rank%d_idx.npy" % rank), np.asarray(self.mine[:n], dtype=np.int64))
         np.save(os.path.join(args.dump_dir, "rank%d_in_head.npy" % rank), np.stack([self.d_in.read(i * self.npix_in, 64, np.uint8) for i in range(n)]))
 
+    def dump_outputs(self, out_dir):
+        """--dump-outputs: the results of the last timed step as a caller receives them (base image, box levels, gradient images), for a
+        sample of frames drawn with a fixed seed: the same arguments give the same files, so two builds can be compared output for output.
+        The files hold finite numbers only: <name>.npy has 0 where the output is not finite (NaN = an overexposed pixel under
+        KILL_OVEREXPOSED, as in the reference), and <name>_nonfinite.npy says what was there (0 finite, 1 NaN, 2 +inf, 3 -inf).  A frame
+        too large for the budget on its own (dso) is sampled as every `stride`-th element of every array."""
+        D = self.D
+        arrays = [("out", self.d_out, self.npix_out)]
+        arrays += [("level%d" % (l + 1), b, (self.out_w >> (l + 1)) * (self.out_h >> (l + 1))) for l, b in enumerate(self.d_levels)]
+        arrays += [("dI%d" % l, b, 3 * (self.out_w >> l) * (self.out_h >> l)) for l, b in enumerate(self.d_dI)]
+        arrays += [("abs%d" % l, b, (self.out_w >> l) * (self.out_h >> l)) for l, b in enumerate(self.d_abs)]
+        budget = DUMP_BUDGET_BYTES // D.world
+        frame_bytes = 2 * 4 * sum(n for _, _, n in arrays)  # values + their non-finite codes
+        stride = -(-frame_bytes // budget)
+        n = max(1, min(self.B, budget // -(-frame_bytes // stride)))
+        local = np.sort(np.random.RandomState(DUMP_SEED).choice(self.B, n, replace=False))
+        prefix = "rank%d_" % D.rank if D.world > 1 else ""
+        os.makedirs(out_dir, exist_ok=True)
+        torch.cuda.synchronize()
+        np.save(os.path.join(out_dir, prefix + "frames.npy"), np.asarray([self.mine[f] for f in local], dtype=np.float64))
+        for name, buf, count in arrays:
+            v = np.stack([buf.read(int(f) * count * 4, count, np.float32)[::stride] for f in local])
+            code = np.zeros(v.shape, np.float32)
+            code[np.isnan(v)] = 1
+            code[np.isposinf(v)] = 2
+            code[np.isneginf(v)] = 3
+            v[code != 0] = 0
+            np.save(os.path.join(out_dir, prefix + name + ".npy"), v)
+            np.save(os.path.join(out_dir, prefix + name + "_nonfinite.npy"), code)
+
     def ceiling(self):
         """Same-box yardstick: the traffic mix of this launch as a linear stream, no arithmetic (rank 0)."""
         ctx, B, stream = self.ctx, self.B, self.stream
@@ -863,6 +916,8 @@ def measure(W, steps, warmup, do_ceiling, parity_frames, min_preroll=None, dump=
     timing = W.timed(steps, warmup)
     if dump:
         W.dump()
+        if W.args.dump_outputs:
+            W.dump_outputs(W.args.dump_outputs)
     if W.D.rank != 0:
         return None
     ceiling = W.ceiling() if do_ceiling else None

@@ -207,7 +207,10 @@ def test_bench_pyramid_checks_every_level():
     out = _bench(["--steps", "3", "--warmup", "1", "--workload", "pyramid", "--frames", "16", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline"])
     par = out["parity"]
     assert (par["frames_checked"], par["levels_checked"], par["mismatching_pixels"]) == (16, 4, 0)  # --frames 16: every frame of the launch
-    assert "libmdc_ref.so" in par["against"] and "unpinned" in par["pinned"]  # base against the reference build; the levels' definition is ours
+    # base against the reference build where it was built (else the C oracle, pinned to the reference's recorded answers); the levels' definition is ours
+    from oracle import loader
+
+    assert ("libmdc_ref.so" if loader.have_ref() else "liboracle.so") in par["against"] and "unpinned" in par["pinned"]
     assert out["roofline"]["kernel"].startswith("remap_strip_kernel<true, true")  # the strip kernel with the fused pyramid ran
 
 
@@ -271,3 +274,70 @@ def test_bench_takes_its_buffers_from_the_product_allocator(strategy):
     plain = _bench(["--steps", "4", "--warmup", "1", "--frames", "1024", "--placement", "first", "--preroll-s", "0.05", "--preroll-max-s", "0.3",
                     "--no-cpu-baseline", "--no-secondary"])
     assert plain["config"]["placement"]["strategy"] == "first" and plain["parity"]["mismatching_pixels"] == 0
+
+
+def _dump_check(dump_dir, workload, world, oracle, stride=None):
+    """bench.py --dump-outputs: every file float32 / float64 and finite, all together under 64 MB; per rank, the base image of every
+    listed frame -- value where the non-finite code is 0, NaN / +inf / -inf where it says so -- equals the oracle's for that GLOBAL frame
+    index (every `stride`-th element where a frame is sampled).  -> {file name: bytes}"""
+    from conftest import bits_equal
+    from mono_dataset_code_amd import capi, synth
+
+    files = sorted(os.listdir(dump_dir))
+    assert sum(os.path.getsize(os.path.join(dump_dir, f)) for f in files) <= 64 * 1000 * 1000
+    got = {}
+    for f in files:
+        a = np.load(os.path.join(dump_dir, f))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        got[f] = a
+    pyr = workload in ("pyramid", "dso")
+    lines = synth.camera_lines(1280, 1024, 1280, 1024) if pyr else synth.CAMERA_1280_TO_640
+    d = synth.write_sequence_calibration(tempfile.mkdtemp(prefix="mdc_dump_"), lines)
+    fov = capi.UndistorterFOV(os.path.join(d, "camera.txt"))
+    photo = capi.PhotometricUndistorter(os.path.join(d, "pcalib.txt"), os.path.join(d, "vignette.png"), 1280, 1024)
+    (rx, ry), ginv, vinv = fov.remap(), photo.ginv(), photo.vignette()[1]
+    ow, oh = fov.dims()[2:]
+    for r in range(world):
+        p = "rank%d_" % r if world > 1 else ""
+        frames = got[p + "frames.npy"]
+        v, code = got[p + "out.npy"].copy(), got[p + "out_nonfinite.npy"]
+        assert set(np.unique(code)) <= {0, 1, 2, 3} and np.all(v[code != 0] == 0)
+        v[code == 1], v[code == 2], v[code == 3] = np.nan, np.inf, -np.inf
+        assert len(frames) == v.shape[0] >= 1 and len(set(frames.tolist())) == len(frames)
+        for i, f in enumerate(frames):
+            assert f == int(f) and int(f) % world == r, (r, f)  # round-robin: rank r holds the global frames r, r + N, ...
+            raw = synth.noise_frames(int(f), 1, 1280 * 1024)[0]
+            want = oracle.get_image(raw, 1280, 1024, ow, oh, ginv, vinv, True, True, rx, ry, 1, 1, 1, 1)
+            assert bits_equal(v[i], want[::stride] if stride else want), (workload, r, int(f))
+    return {f: open(os.path.join(dump_dir, f), "rb").read() for f in files}
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat_and_match_the_oracle(tmp_path, oracle):
+    """Two runs of the headline with the same arguments write the same files, byte for byte, and the sampled frames are the oracle's."""
+    args = ["--steps", "3", "--warmup", "1", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline", "--no-ceiling"]
+    dumps = []
+    for run in ("a", "b"):
+        out = _bench(args + ["--dump-outputs", str(tmp_path / run)])
+        assert out["steps"] == 3 and out["parity"]["mismatching_pixels"] == 0
+        dumps.append(_dump_check(str(tmp_path / run), "fused", 1, oracle))
+    assert sorted(dumps[0]) == ["frames.npy", "out.npy", "out_nonfinite.npy"]
+    assert dumps[0] == dumps[1]
+    assert np.load(str(tmp_path / "a" / "out_nonfinite.npy")).any()  # the overexposed pixels of the noise frames are there, coded
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload,world,frames,stride", [("pyramid", 1, 8, None), ("dso", 1, 4, 2), ("dso", 2, 4, 3)])
+def test_bench_dump_outputs_stay_within_64_mb(tmp_path, oracle, workload, world, frames, stride):
+    """The larger workloads, one rank and two (gloo, sharing the GPU): every output array is written (levels, gradient images), the
+    whole directory stays under 64 MB, a frame too large on its own is sampled every `stride`-th element, and the base images are the oracle's."""
+    args = ["--steps", "2", "--warmup", "1", "--workload", workload, "--frames", str(frames), "--preroll-s", "0.05", "--preroll-max-s", "0.2",
+            "--no-cpu-baseline", "--no-ceiling", "--dump-outputs", str(tmp_path)]
+    if world == 1:
+        _bench(args)
+    else:
+        _bench(["--gpus", str(world)] + args, env={"MDC_BENCH_BACKEND": "gloo"}, nproc=world, port=29543)
+    dump = _dump_check(str(tmp_path), workload, world, oracle, stride)
+    names = ["out", "level1", "level2", "level3"] + (["dI%d" % l for l in range(4)] + ["abs%d" % l for l in range(4)] if workload == "dso" else [])
+    prefixes = ["rank%d_" % r for r in range(world)] if world > 1 else [""]
+    assert sorted(dump) == sorted([p + "frames.npy" for p in prefixes] + [p + n + s for p in prefixes for n in names for s in (".npy", "_nonfinite.npy")])

@@ -42,13 +42,8 @@ def problem(seed=0, n=6, wI=48, hI=40, gw=36, gh=30):
     return images, p2x, p2y, gw, gh
 
 
-def test_oracle_equals_reference_loops_bit_for_bit(oracle):
-    from oracle import loader
-
-    try:
-        ref = loader.VcalRef()
-    except OSError as e:
-        pytest.skip(str(e))
+def test_oracle_equals_reference_loops_bit_for_bit(oracle, vcal_ref):
+    ref = vcal_ref
     for seed in range(3):
         images, p2x, p2y, gw, gh = problem(seed)
         n, hI, wI = images.shape
@@ -207,14 +202,9 @@ def _smooth_cases():
         yield w, h, v
 
 
-def test_oracle_smoothing_equals_reference_text(oracle):
+def test_oracle_smoothing_equals_reference_text(oracle, vcal_ref):
     """The output smoothing :541-566 (four NaN-aware 3 x 3 mean passes): oracle == the reference's own lines."""
-    from oracle import loader
-
-    try:
-        ref = loader.VcalRef()
-    except OSError as e:
-        pytest.skip(str(e))
+    ref = vcal_ref
     for w, h, v in _smooth_cases():
         for got, want in zip(oracle.vcal_smooth(v, w, h), ref.smooth(v, w, h)):
             assert bits_equal(got, want), (w, h)
@@ -248,14 +238,9 @@ def _coord_cases():
     return gw, gh, wI, hI, x, y
 
 
-def test_oracle_coordinate_mask_equals_reference_text(oracle):
+def test_oracle_coordinate_mask_equals_reference_text(oracle, vcal_ref):
     """:345-357 (NaN coordinates for plane points outside the image), NaN / inf / out-of-int-range inputs included."""
-    from oracle import loader
-
-    try:
-        ref = loader.VcalRef()
-    except OSError as e:
-        pytest.skip(str(e))
+    ref = vcal_ref
     gw, gh, wI, hI, x, y = _coord_cases()
     for got, want in zip(oracle.vcal_mask_coords(x, y, wI, hI), ref.mask_coords(x, y, gw, gh, wI, hI)):
         assert bits_equal(got, want)
@@ -286,14 +271,9 @@ def _gradient_cases():
         yield w, h, th, img
 
 
-def test_oracle_gradient_mask_equals_reference_text(oracle):
+def test_oracle_gradient_mask_equals_reference_text(oracle, vcal_ref):
     """:293-301, the in-place, order-dependent gradient mask of a calibration image: oracle == the reference's own lines."""
-    from oracle import loader
-
-    try:
-        ref = loader.VcalRef()
-    except OSError as e:
-        pytest.skip(str(e))
+    ref = vcal_ref
     for w, h, th, img in _gradient_cases():
         assert bits_equal(oracle.vcal_gradient_mask(img, th), ref.gradient_mask(img, th)), (w, h)
 
