@@ -513,6 +513,75 @@ MDC_API int mdc_vcal_mask_coords_device(mdc_ctx* ctx, float* d_x, float* d_y, in
 MDC_API int mdc_vcal_smooth_device(mdc_ctx* ctx, const float* d_vignette_factor, int w, int h, float* d_smoothed, float* d_scratch,
                            void* stream);
 
+/* ---- responseCalib solver (src/main_responseCalib.cpp:177-380) --------------------------------------- */
+
+/* An exposure sweep on the device: d_images = n_images stacked w x h 8-bit frames (what getImageRaw gives, e.g. through
+ * DatasetReader::getImagesRawDevice), d_exposure = their n_images exposure times as doubles (:202).  d_G = 256 doubles (the
+ * inverse response, what pcalib.txt holds), d_E = w*h doubles (the scene irradiance).  rmse results are pairs {rmse, num} in
+ * DEVICE memory: {1e5 * sqrt(e / num), num} of :50-69 (num exact; rmse within 1e-9 relative in the tests -- the reference sums in long
+ * double, these sums are double-double in a fixed order).  Every call is deterministic; the step calls synchronise `stream`
+ * (their scratch is freed before they return).  Without a GPU (ctx == NULL) every entry returns MDC_ERR_NO_DEVICE. */
+
+/* Leak padding (:208-233), in place, leak_padding passes per image: every interior pixel (1 <= x <= w-2, 1 <= y <= h-2) of value
+ * 255 sets its 3 x 3 neighbourhood to 255.  Exact. */
+MDC_API int mdc_rcal_leak_pad_device(mdc_ctx* ctx, uint8_t* d_images, int n_images, int w, int h, int leak_padding, void* stream);
+/* Initial irradiance (:250-258): E[k] = mean of the n_images bytes of pixel k, 255 included.  Exact. */
+MDC_API int mdc_rcal_init_e_device(mdc_ctx* ctx, const uint8_t* d_images, int n_images, int w, int h, double* d_E, void* stream);
+/* rmse(G, E) (:50-69) -> d_out[2]. */
+MDC_API int mdc_rcal_rmse_device(mdc_ctx* ctx, const uint8_t* d_images, const double* d_exposure, int n_images, int w, int h,
+                         const double* d_G, const double* d_E, double* d_out, void* stream);
+/* G step (:285-304), DIRECT: one streaming pass, GSum in 128-bit fixed point per workgroup, combined in a fixed order.
+ * Deterministic; within 1e-9 relative of the reference's sequential sums (tests/test_rcal.py), not bitwise.  d_G <- GSum / GNum, non-finite
+ * entries from index 2 on extrapolated (G[255] always is). */
+MDC_API int mdc_rcal_g_step_device(mdc_ctx* ctx, const uint8_t* d_images, const double* d_exposure, int n_images, int w, int h,
+                           const double* d_E, double* d_G, void* stream);
+/* G step in the reference's EXACT ORDER.  The byte values never change over the iterations, so mdc_rcal_index_create sorts the
+ * stack once by value, stably: per bin the positions i*w*h + k of its samples in the reference's (i-major, k-ascending) order,
+ * 4 bytes per sample of value < 255 while n*w*h < 2^32, 8 above (checked against free device memory: MDC_ERR_NOMEM with the
+ * sizes in mdc_last_error).  mdc_rcal_g_step_indexed_device then walks each bin's list as one sequential double chain: GSum,
+ * G, and with them E and pcalib.txt, are bit-identical to the reference.  Its time is bounded by the longest chain
+ * (mdc_rcal_index_longest_chain).  The index belongs to the (leak-padded) stack it was built from; building it synchronises
+ * `stream`. */
+typedef struct mdc_rcal_index mdc_rcal_index;
+MDC_API int mdc_rcal_index_create(mdc_ctx* ctx, const uint8_t* d_images, int n_images, int w, int h, void* stream, mdc_rcal_index** out);
+MDC_API void mdc_rcal_index_destroy(mdc_rcal_index* index);
+MDC_API int64_t mdc_rcal_index_bytes(const mdc_rcal_index* index);         /* device bytes of the position lists */
+MDC_API int64_t mdc_rcal_index_entries(const mdc_rcal_index* index);       /* samples listed (value < 255) */
+MDC_API int64_t mdc_rcal_index_longest_chain(const mdc_rcal_index* index); /* samples of the most populated bin */
+MDC_API int mdc_rcal_g_step_indexed_device(mdc_ctx* ctx, const mdc_rcal_index* index, const double* d_exposure, const double* d_E,
+                                   double* d_G, void* stream);
+/* E step (:319-339), per pixel the images in order: E = max(ESum / ENum, 0) (NaN where every sample is 255), in place;
+ * bit-identical to the reference for the same G.  d_rmse_g (may be NULL) <- rmse(G, E before the step), the reference's
+ * "optG RMSE" (:303). */
+MDC_API int mdc_rcal_e_step_device(mdc_ctx* ctx, const uint8_t* d_images, const double* d_exposure, int n_images, int w, int h,
+                           const double* d_G, double* d_E, double* d_rmse_g, void* stream);
+/* Rescale (:349-356): f = 255 / G[255]; E *= f; G[i] *= f for i < min(256, w*h) only (the reference's loop bound).
+ * d_rmse_e (may be NULL) <- rmse before ("OptE RMSE", :336), d_rmse_resc (may be NULL) <- after ("resc RMSE", :357). */
+MDC_API int mdc_rcal_rescale_device(mdc_ctx* ctx, const uint8_t* d_images, const double* d_exposure, int n_images, int w, int h,
+                            double* d_G, double* d_E, double* d_rmse_e, double* d_rmse_resc, void* stream);
+
+/* The whole solve (:250-358) on an already leak-padded stack: G = 0, E = initial mean, then `iterations` times G step, E step,
+ * rescale, everything on `stream`, one synchronisation at the end (plus the index build's in exact-order mode).  d_G and d_E
+ * receive the final G (pcalib.txt) and E.  MDC_RCAL_EXACT_ORDER: bit-identical to the reference; MDC_RCAL_DIRECT: no index,
+ * deterministic, within 1e-9 relative of the exact order (tests/test_rcal.py).  log (host, may be NULL): init rmse / num and, in log->iters (caller-allocated, `iterations`
+ * entries), what the reference prints per iteration; rmse_resc / num_resc are its log.txt columns (:360). */
+#define MDC_RCAL_EXACT_ORDER 0u
+#define MDC_RCAL_DIRECT 1u
+typedef struct mdc_rcal_iter {
+  double rmse_G, num_G;       /* after the G step */
+  double rmse_E, num_E;       /* after the E step */
+  double rmse_resc, num_resc; /* after the rescale */
+  double rescale;             /* the factor 255 / G[255] */
+} mdc_rcal_iter;
+typedef struct mdc_rcal_log {
+  double init_rmse, init_num;
+  mdc_rcal_iter* iters;
+} mdc_rcal_log;
+MDC_API int mdc_rcal_solve_device(mdc_ctx* ctx, const uint8_t* d_images, const double* d_exposure, int n_images, int w, int h,
+                          int iterations, unsigned mode, double* d_G, double* d_E, mdc_rcal_log* log, void* stream);
+/* Blocking copy to device memory of the context's GPU from host or device memory (the counterpart of mdc_copy_to_host). */
+MDC_API int mdc_copy_to_device(mdc_ctx* ctx, void* d_dst, const void* src, size_t bytes);
+
 /* Plan selection by measurement.  Which tile shape and workgroup length is fastest depends on the remap (window sizes)
  * and, by a few per cent, on the individual GPU (profiles/r02_experiments/04_*, 13_*).  mdc_tune_device runs the fused
  * pass (flags must contain MDC_RECTIFY) over the caller's device batch with each candidate -- tile 128x16 / 64x32 /

@@ -79,6 +79,9 @@ MDC_API int mdch_reader_get_images_device(mdch_reader*, int first, int count, in
 MDC_API mdc_ctx* mdch_reader_context(mdch_reader*);
 MDC_API int mdch_reader_device(mdch_reader*);
 MDC_API int mdch_reader_get_raw(mdch_reader*, int id, unsigned char* out, long cap, int wh[2]); /* getImageRaw(); 1 / 0 */
+/* getImagesRawDevice(first, count, step, d_out, valid): raw u8 frames into a device array; returns the number delivered */
+MDC_API int mdch_reader_get_images_raw_device(mdch_reader*, int first, int count, int step, unsigned char* d_out, unsigned char* valid);
+MDC_API void mdch_reader_raw_dims(mdch_reader*, int wh[2]); /* getRawSize() */
 MDC_API void mdch_reader_set_threads(mdch_reader*, int n);       /* setDecodeThreads() */
 MDC_API void mdch_reader_set_prefetch(mdch_reader*, int frames); /* setPrefetch() */
 MDC_API void mdch_reader_set_lookahead(mdch_reader*, int frames); /* setResultLookahead(): getImage results made ahead on JPEG sequences read in order */

@@ -74,6 +74,14 @@ class MDC_API DatasetReader {
   // the first one: shard with one reader per device, frame f on device f % N.
   int getImagesDevice(int first, int count, bool rectify, bool removeGamma, bool removeVignette, bool nanOverexposed,
                       const struct mdc_device_outputs* out, unsigned char* valid);
+  // Raw 8-bit frames first, first+step, ... (count of them) straight into the DEVICE array d_out (count x w*h bytes, frame j at
+  // j*w*h; w x h = getRawSize()): the bytes of getImageRaw, decoded by the thread pool and uploaded -- what the responseCalib
+  // solver (include/mdc_hip.h: mdc_rcal_*) reads.  valid[j] (optional, `count` bytes) = 1 where position j holds a frame, 0 for
+  // an undecodable or wrong-sized one or an id past the end.  d_out lives on the reader's device (getDevice(), or the current
+  // device when the folder has no calibration).  Returns the number of frames delivered.
+  int getImagesRawDevice(int first, int count, int step, unsigned char* d_out, unsigned char* valid);
+  // The size of the raw frames: camera.txt's input size, or -- in a sweep folder without camera.txt -- the first decodable frame's.
+  void getRawSize(int* width, int* height) const;
   struct mdc_ctx* getContext();  // the GPU context behind getImage / getImages / getImagesDevice (0 without a GPU)
   int getDevice() const;         // its HIP device ordinal (-1 without a GPU)
 

@@ -23,7 +23,7 @@ LIB_HIP = os.path.join(PKG, "libmdc_hip.so")
 LIB_HOST = os.path.join(PKG, "libmdc_host.so")
 
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("mdc_kernels.hip", "mdc_vcal.hip", "mdc_jpeg.hip", "mdc_capi.hip", "mdc_plan.hip", "mdc_host_calls.hip",
-                                                "mdc_pipeline.hip", "mdc_placement.hip")]
+                                                "mdc_pipeline.hip", "mdc_placement.hip", "mdc_rcal.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "mdc_exports.map"), os.path.join(CSRC, "mdc_internal.h"), os.path.join(CSRC, "mdc_ctx.h"), os.path.join(CSRC, "mdc_build_config.h"), os.path.join(CSRC, "fov_point_model.h"), os.path.join(CSRC, "placement_classes.h"), os.path.join(INC, "mdc_hip.h")]
 HOST_SOURCES = [os.path.join(HOST, f) for f in (
     "fov_undistorter.cpp", "photometric_undistorter.cpp", "gray_png.cpp", "host_device.cpp", "mdc_host_capi.cpp",
@@ -190,6 +190,22 @@ def build_host(force=False):
     return LIB_HOST
 
 
+BIN = os.path.join(PKG, "bin")
+RESPONSE_CALIB = os.path.join(BIN, "responseCalib")
+RESPONSE_CALIB_SOURCE = os.path.join(CSRC, "programs", "responseCalib.cpp")
+
+
+def build_programs(force=False):
+    """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so."""
+    build_host(force)
+    os.makedirs(BIN, exist_ok=True)
+    deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
+    if force or _stale(RESPONSE_CALIB, deps):
+        _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
+              RESPONSE_CALIB_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-Wl,-rpath,$ORIGIN/..", "-o", RESPONSE_CALIB])
+    return RESPONSE_CALIB
+
+
 LIB_BENCH = os.path.join(PKG, "libmdc_bench.so")
 BENCH_SOURCE = os.path.join(CSRC, "bench", "mdc_bench.hip")
 
@@ -268,6 +284,7 @@ def build_fault_injection():
 def build_all(force=False):
     build_hip(force)
     build_host(force)
+    build_programs(force)
     build_multi(force)
     build_bench(force)
     build_debug()

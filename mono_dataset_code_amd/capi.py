@@ -40,6 +40,9 @@ HIP_SYMBOLS = [
     "mdc_vcal_vignette_step_device", "mdc_gradients_batch_device", "mdc_process_pyramid_gradients_batch_device", "mdc_tune_device",
     "mdc_vcal_index_create", "mdc_vcal_index_destroy", "mdc_vcal_index_bytes", "mdc_vcal_index_entries",
     "mdc_vcal_vignette_step_indexed_device", "mdc_vcal_solve_device", "mdc_vcal_smooth_device", "mdc_vcal_mask_coords_device", "mdc_vcal_gradient_mask_device", "mdc_vcal_scale_images_device",
+    "mdc_rcal_leak_pad_device", "mdc_rcal_init_e_device", "mdc_rcal_rmse_device", "mdc_rcal_g_step_device", "mdc_rcal_index_create",
+    "mdc_rcal_index_destroy", "mdc_rcal_index_bytes", "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain",
+    "mdc_rcal_g_step_indexed_device", "mdc_rcal_e_step_device", "mdc_rcal_rescale_device", "mdc_rcal_solve_device", "mdc_copy_to_device",
 ]
 HOST_SYMBOLS = [
     "mdch_fov_create", "mdch_fov_destroy", "mdch_fov_valid", "mdch_fov_has_gpu", "mdch_fov_dims",
@@ -50,12 +53,25 @@ HOST_SYMBOLS = [
     "mdch_reader_dims", "mdch_reader_get_image", "mdch_reader_get_images", "mdch_reader_get_images_device", "mdch_reader_context", "mdch_reader_device", "mdch_reader_get_raw", "mdch_reader_set_threads",
     "mdch_reader_set_prefetch", "mdch_reader_set_gpu_jpeg", "mdch_reader_set_lookahead", "mdch_reader_last_error", "mdch_reader_prefetch_stats", "mdch_reader_device_stats", "mdch_decode_gray8", "mdch_jpeg_record_bytes",
     "mdch_decode_jpeg_record", "mdch_jpeg_stream", "mdch_image_alloc", "mdch_image_free",
-    "mdch_image_pool_trim", "mdch_image_pool_idle_bytes",
+    "mdch_image_pool_trim", "mdch_image_pool_idle_bytes", "mdch_reader_get_images_raw_device", "mdch_reader_raw_dims",
 ]
 
 
 PLACE_AUTO, PLACE_FIRST, PLACE_MALLOC, PLACE_VMM = 0, 1, 2, 3
 PLACE_NAMES = {PLACE_AUTO: "auto", PLACE_FIRST: "first", PLACE_MALLOC: "malloc", PLACE_VMM: "vmm"}
+
+
+RCAL_EXACT_ORDER, RCAL_DIRECT = 0, 1
+
+
+class RcalIter(C.Structure):
+    """mdc_rcal_iter (include/mdc_hip.h)"""
+    _fields_ = [(n, C.c_double) for n in ("rmse_G", "num_G", "rmse_E", "num_E", "rmse_resc", "num_resc", "rescale")]
+
+
+class RcalLog(C.Structure):
+    """mdc_rcal_log (include/mdc_hip.h)"""
+    _fields_ = [("init_rmse", C.c_double), ("init_num", C.c_double), ("iters", C.POINTER(RcalIter))]
 
 
 class PlacedBuffers(C.Structure):
@@ -255,11 +271,28 @@ def hip_lib():
             L.mdc_vcal_mask_coords_device.argtypes = [_vp, _vp, _vp, C.c_int64, _i, _i, _vp]
             L.mdc_vcal_gradient_mask_device.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
             L.mdc_vcal_scale_images_device.argtypes = [_vp, _vp, _i, C.c_int64, C.c_float, _vp, _vp]
+        if not old_build or hasattr(L, "mdc_rcal_solve_device"):
+            L.mdc_rcal_leak_pad_device.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
+            L.mdc_rcal_init_e_device.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
+            L.mdc_rcal_rmse_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]
+            L.mdc_rcal_g_step_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]
+            L.mdc_rcal_index_create.argtypes = [_vp, _vp, _i, _i, _i, _vp, C.POINTER(_vp)]
+            L.mdc_rcal_index_destroy.argtypes = [_vp]
+            L.mdc_rcal_index_destroy.restype = None
+            for n in ("mdc_rcal_index_bytes", "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain"):
+                getattr(L, n).argtypes = [_vp]
+                getattr(L, n).restype = C.c_int64
+            L.mdc_rcal_g_step_indexed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
+            L.mdc_rcal_e_step_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]
+            L.mdc_rcal_rescale_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
+            L.mdc_rcal_solve_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, C.c_uint, _vp, _vp, C.POINTER(RcalLog), _vp]
+            L.mdc_copy_to_device.argtypes = [_vp, _vp, _vp, _sz]
         for n in HIP_SYMBOLS:
             if old_build and not hasattr(L, n):
                 continue
             if n not in ("mdc_destroy", "mdc_last_error", "mdc_build_flags", "mdc_code_id", "mdc_device_free", "mdc_host_alloc", "mdc_host_free", "mdc_vcal_index_destroy",
-                         "mdc_vcal_index_bytes", "mdc_vcal_index_entries"):
+                         "mdc_vcal_index_bytes", "mdc_vcal_index_entries", "mdc_rcal_index_destroy", "mdc_rcal_index_bytes",
+                         "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain"):
                 getattr(L, n).restype = _i
         _hip = L
     return _hip
@@ -342,6 +375,10 @@ def host_lib():
         L.mdch_reader_context.restype = _vp
         L.mdch_reader_device.argtypes = [_vp]
         L.mdch_reader_get_raw.argtypes = [_vp, _i, _vp, C.c_long, _vp]
+        if hasattr(L, "mdch_reader_get_images_raw_device"):
+            L.mdch_reader_get_images_raw_device.argtypes = [_vp, _i, _i, _i, _vp, _vp]
+            L.mdch_reader_raw_dims.argtypes = [_vp, _vp]
+            L.mdch_reader_raw_dims.restype = None
         L.mdch_reader_set_threads.argtypes = [_vp, _i]
         L.mdch_reader_set_threads.restype = None
         L.mdch_reader_set_prefetch.argtypes = [_vp, _i]
@@ -733,6 +770,85 @@ class Context:
         e, r = er.cpu().tolist()
         return tt, ct, e, r
 
+    # ---- responseCalib (include/mdc_hip.h); d_images: (n, h, w) uint8, d_exposure: (n,) float64, d_G: (256,) float64,
+    # d_E: (h, w) or (h*w,) float64 -- torch device tensors
+    def rcal_leak_pad(self, d_images, leak_padding=2, stream=0):
+        """Leak padding (src/main_responseCalib.cpp:208-233), in place."""
+        n, h, w = d_images.shape
+        self._chk(self._L.mdc_rcal_leak_pad_device(self._h, d_images.data_ptr(), n, w, h, int(leak_padding), stream if stream else None))
+
+    def rcal_init_e(self, d_images, stream=0):
+        """Initial irradiance (:250-258) -> E (h*w float64)."""
+        import torch
+
+        n, h, w = d_images.shape
+        E = torch.empty(h * w, dtype=torch.float64, device=d_images.device)
+        self._chk(self._L.mdc_rcal_init_e_device(self._h, d_images.data_ptr(), n, w, h, E.data_ptr(), stream if stream else None))
+        return E
+
+    def _rcal_pair(self, d):
+        import torch
+
+        return torch.zeros(2, dtype=torch.float64, device=d.device)
+
+    def rcal_rmse(self, d_images, d_exposure, d_G, d_E, stream=0):
+        """rmse(G, E) (:50-69) -> (rmse, num)."""
+        n, h, w = d_images.shape
+        out = self._rcal_pair(d_images)
+        self._chk(self._L.mdc_rcal_rmse_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_G.data_ptr(), d_E.data_ptr(),
+                                               out.data_ptr(), stream if stream else None))
+        a, b = out.cpu().tolist()
+        return a, b
+
+    def rcal_g_step(self, d_images, d_exposure, d_E, d_G, stream=0):
+        """G step (:285-304), direct (fixed-point) mode; d_G is overwritten."""
+        n, h, w = d_images.shape
+        self._chk(self._L.mdc_rcal_g_step_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_E.data_ptr(), d_G.data_ptr(),
+                                                 stream if stream else None))
+
+    def rcal_index(self, d_images, stream=0):
+        """Exact-order index of the stack (mdc_rcal_index_create)."""
+        return RcalIndex(self, d_images, stream)
+
+    def rcal_g_step_indexed(self, index, d_exposure, d_E, d_G, stream=0):
+        """G step in the reference's order (bit-identical); d_G is overwritten."""
+        self._chk(self._L.mdc_rcal_g_step_indexed_device(self._h, index._h, d_exposure.data_ptr(), d_E.data_ptr(), d_G.data_ptr(),
+                                                         stream if stream else None))
+
+    def rcal_e_step(self, d_images, d_exposure, d_G, d_E, stream=0):
+        """E step (:319-339), d_E in place -> (rmse, num) of G with the E before the step."""
+        n, h, w = d_images.shape
+        out = self._rcal_pair(d_images)
+        self._chk(self._L.mdc_rcal_e_step_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_G.data_ptr(), d_E.data_ptr(),
+                                                 out.data_ptr(), stream if stream else None))
+        a, b = out.cpu().tolist()
+        return a, b
+
+    def rcal_rescale(self, d_images, d_exposure, d_G, d_E, stream=0):
+        """Rescale (:349-356), d_G and d_E in place -> ((rmse, num) before, (rmse, num) after)."""
+        n, h, w = d_images.shape
+        a, b = self._rcal_pair(d_images), self._rcal_pair(d_images)
+        self._chk(self._L.mdc_rcal_rescale_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_G.data_ptr(), d_E.data_ptr(),
+                                                  a.data_ptr(), b.data_ptr(), stream if stream else None))
+        return tuple(a.cpu().tolist()), tuple(b.cpu().tolist())
+
+    def rcal_solve(self, d_images, d_exposure, iterations=10, mode=RCAL_EXACT_ORDER, stream=0):
+        """The whole solve (:250-358) on a leak-padded stack -> (G (256,) float64, E (h*w,) float64 device tensors,
+        log dict: init_rmse, init_num, iters = list of per-iteration dicts)."""
+        import torch
+
+        n, h, w = d_images.shape
+        G = torch.empty(256, dtype=torch.float64, device=d_images.device)
+        E = torch.empty(h * w, dtype=torch.float64, device=d_images.device)
+        its = (RcalIter * max(int(iterations), 1))()
+        lg = RcalLog(0.0, 0.0, C.cast(its, C.POINTER(RcalIter)))
+        self._chk(self._L.mdc_rcal_solve_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, int(iterations), int(mode),
+                                                G.data_ptr(), E.data_ptr(), C.byref(lg), stream if stream else None))
+        names = [f[0] for f in RcalIter._fields_]
+        log = {"init_rmse": lg.init_rmse, "init_num": lg.init_num,
+               "iters": [{k: getattr(its[i], k) for k in names} for i in range(int(iterations))]}
+        return G, E, log
+
     def bind(self, fov=None, photo=None):
         rc = host_lib().mdch_bind(self._h, fov._h if fov is not None else None, photo._h if photo is not None else None)
         self._chk(rc)
@@ -753,6 +869,30 @@ class VcalIndex:
     def close(self):
         if self._h:
             self._L.mdc_vcal_index_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RcalIndex:
+    """mdc_rcal_index: per byte value, the positions of its samples in the reference's (image, pixel) order."""
+
+    def __init__(self, ctx, d_images, stream=0):
+        self._L = ctx._L
+        self._h = _vp()
+        n, self.h, self.w = d_images.shape
+        ctx._chk(self._L.mdc_rcal_index_create(ctx._h, d_images.data_ptr(), n, self.w, self.h, stream if stream else None, C.byref(self._h)))
+        self.bytes = self._L.mdc_rcal_index_bytes(self._h)
+        self.entries = self._L.mdc_rcal_index_entries(self._h)
+        self.longest_chain = self._L.mdc_rcal_index_longest_chain(self._h)
+
+    def close(self):
+        if self._h:
+            self._L.mdc_rcal_index_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):
@@ -1005,6 +1145,19 @@ class DatasetReader:
         """getImagesDevice: results into the device arrays of `outputs` (DeviceOutputs; frame first + i at position i) -> (valid mask, number produced)."""
         valid = np.zeros(count, np.uint8)
         got = self._L.mdch_reader_get_images_device(self._h, first, count, int(rectify), int(g), int(v), int(o), C.byref(outputs), _np_ptr(valid))
+        return valid.astype(bool), got
+
+    def raw_dims(self):
+        """getRawSize() -> (w, h)"""
+        wh = np.zeros(2, np.int32)
+        self._L.mdch_reader_raw_dims(self._h, _np_ptr(wh))
+        return int(wh[0]), int(wh[1])
+
+    def get_images_raw_device(self, first, count, step, d_out):
+        """getImagesRawDevice: frames first, first+step, ... as u8 into the device tensor d_out (count x w*h bytes, w x h = the
+        reader's frame size) -> (valid mask, number delivered)."""
+        valid = np.zeros(count, np.uint8)
+        got = self._L.mdch_reader_get_images_raw_device(self._h, int(first), int(count), int(step), d_out.data_ptr(), _np_ptr(valid))
         return valid.astype(bool), got
 
     def device(self):

@@ -130,7 +130,12 @@ struct DatasetReader::State {
   void* multi = 0;  // libmdc_multi.so's object when the lanes' contexts are its (RCCL table broadcast), else the lanes own theirs
   std::mutex err_mu, image_mu;
 
-  size_t frame_bytes() const { return (size_t)W * H; }
+  // frame size of a sweep folder without camera.txt (responseCalib needs only images + times.txt): the first decodable frame's
+  int RW = 0, RH = 0;
+  mdc_ctx* raw_gpu = 0;  // getImagesRawDevice's context when the reader has none of its own (no calibration to bind)
+  size_t frame_bytes() const { return W > 0 && H > 0 ? (size_t)W * H : (size_t)RW * RH; }
+  int frame_w() const { return W > 0 && H > 0 ? W : RW; }
+  int frame_h() const { return W > 0 && H > 0 ? H : RH; }
   // GPU JPEG stage of getImages: JPEG frames travel as coefficient records (2 bytes per pixel + table), the inverse DCT runs on
   // the device.  Default on; MDC_GPU_JPEG=0 or setGpuJpeg(false) keeps the whole decode on the host.
   int gpu_jpeg = 2;  // 0: JPEG decoded on the host; 1: host Huffman + device inverse DCT; 2: device Huffman + inverse DCT
@@ -629,6 +634,23 @@ DatasetReader::DatasetReader(std::string folder) : s_(new State()) {
   s.H = s.fov->getInputDims()[1];
   s.w = s.fov->getOutputDims()[0];
   s.h = s.fov->getOutputDims()[1];
+  if (s.W <= 0 || s.H <= 0) {  // no (valid) camera.txt: the raw frames still have a size -- the first decodable frame's
+    std::vector<unsigned char> buf;
+    for (int id = 0; id < (int)s.files.size() && !s.RW; id++) {
+      Decode d;
+      d.id = id;
+      s.decode_now(d);  // cap 0: fails, but a parsed header leaves the size behind
+      if (d.w <= 0 || d.h <= 0) continue;
+      buf.resize((size_t)d.w * d.h);
+      d.dst = buf.data();
+      d.cap = buf.size();
+      s.decode_now(d);
+      if (d.ok) {
+        s.RW = d.w;
+        s.RH = d.h;
+      }
+    }
+  }
 
   // one context holding BOTH objects' tables: the fused pass needs them together -- per device the reader may use
   // (MDC_DEVICES=all | 0,1,...; unset: the one device of $MDC_DEVICE / the calling thread, as before)
@@ -642,6 +664,7 @@ DatasetReader::~DatasetReader() {
   for (auto& m : s.slot_mem) m.release();
   s.drop_ahead();
   s.close_devices();
+  if (s.raw_gpu) mdc_destroy(s.raw_gpu);
   delete s.fov;
   delete s.photo;
   delete s_;
@@ -1044,6 +1067,95 @@ int DatasetReader::getImagesDevice(int first, int count, bool rectify, bool remo
     return 0;
   }
   return run_batch(first, count, rectify, removeGamma, removeVignette, nanOverexposed, 0, out, valid);
+}
+
+void DatasetReader::getRawSize(int* width, int* height) const {
+  if (width) *width = s_->frame_w();
+  if (height) *height = s_->frame_h();
+}
+
+// Raw frames for the responseCalib solver: the decode pool fills a page-locked block of up to 64 frames, which goes up frame by
+// frame (contiguous runs of valid frames in one copy); the next block is decoded after the upload of the previous one.
+int DatasetReader::getImagesRawDevice(int first, int count, int step, unsigned char* d_out, unsigned char* valid) {
+  State& s = *s_;
+  s.err.clear();
+  if (count <= 0) return 0;
+  if (valid) std::memset(valid, 0, (size_t)count);
+  if (step < 1 || !d_out) {
+    s.err = "getImagesRawDevice: bad argument";
+    return 0;
+  }
+  const size_t fb = s.frame_bytes();
+  if (!fb) {
+    s.err = "getImagesRawDevice: no decodable frame, the frame size is unknown";
+    return 0;
+  }
+  mdc_ctx* ctx = s.gpu;
+  if (!ctx) {
+    if (!s.raw_gpu) s.raw_gpu = mdc_host::open_device_context("DatasetReader");
+    ctx = s.raw_gpu;
+  }
+  if (!ctx) {
+    s.err = "getImagesRawDevice: no GPU";
+    return 0;
+  }
+  const int kBatch = 64;
+  const int per = std::min(kBatch, count);
+  HostBuffer block;
+  block.alloc((size_t)per * fb);
+  std::vector<Decode> jobs((size_t)per);
+  s.start_pool();
+  int got = 0;
+  for (int j0 = 0; j0 < count; j0 += per) {
+    const int m = std::min(per, count - j0);
+    {
+      std::lock_guard<std::mutex> lk(s.mu);
+      for (int q = 0; q < m; q++) {
+        Decode& d = jobs[(size_t)q];
+        d = Decode();
+        d.id = (int)std::min<long long>((long long)first + (long long)(j0 + q) * step, (long long)s.files.size());
+        if (first < 0) d.id = -1;
+        d.dst = block.p + (size_t)q * fb;
+        d.cap = fb;
+        s.submit(&d);
+      }
+    }
+    s.cv_job.notify_all();
+    {
+      std::unique_lock<std::mutex> lk(s.mu);
+      s.cv_done.wait(lk, [&] {
+        for (int q = 0; q < m; q++)
+          if (!jobs[(size_t)q].done) return false;
+        return true;
+      });
+    }
+    for (int q = 0; q < m;) {
+      auto good = [&](int k) {
+        const Decode& d = jobs[(size_t)k];
+        return d.ok && d.w == s.frame_w() && d.h == s.frame_h();
+      };
+      if (!good(q)) {
+        const Decode& d = jobs[(size_t)q];
+        if (s.err.empty()) s.err = d.ok ? s.files[(size_t)d.id] + ": wrong frame size" : d.err;
+        q++;
+        continue;
+      }
+      int r = q + 1;
+      while (r < m && good(r)) r++;
+      const int rc = mdc_copy_to_device(ctx, d_out + (size_t)(j0 + q) * fb, block.p + (size_t)q * fb, (size_t)(r - q) * fb);
+      if (rc != MDC_OK) {
+        s.err = std::string("getImagesRawDevice: ") + mdc_last_error(ctx);
+        block.release();
+        return got;
+      }
+      for (int k = q; k < r; k++)
+        if (valid) valid[j0 + k] = 1;
+      got += r - q;
+      q = r;
+    }
+  }
+  block.release();
+  return got;
 }
 
 mdc_ctx* DatasetReader::getContext() { return s_->gpu; }

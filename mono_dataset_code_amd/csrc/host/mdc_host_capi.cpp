@@ -273,6 +273,10 @@ int mdch_reader_get_raw(mdch_reader* h, int id, unsigned char* out, long cap, in
   memcpy(out, p, (size_t)wh[0] * wh[1]);
   return 1;
 } catch (...) { return {}; }  // no exception leaves the C facade
+int mdch_reader_get_images_raw_device(mdch_reader* h, int first, int count, int step, unsigned char* d_out, unsigned char* valid) try {
+  return h->r->getImagesRawDevice(first, count, step, d_out, valid);
+} catch (...) { return 0; }
+void mdch_reader_raw_dims(mdch_reader* h, int wh[2]) try { h->r->getRawSize(&wh[0], &wh[1]); } catch (...) {}
 void mdch_reader_set_threads(mdch_reader* h, int n) try { h->r->setDecodeThreads(n); } catch (...) {}
 void mdch_reader_set_prefetch(mdch_reader* h, int n) try { h->r->setPrefetch(n); } catch (...) {}
 void mdch_reader_set_lookahead(mdch_reader* h, int frames) try { h->r->setResultLookahead(frames); } catch (...) {}

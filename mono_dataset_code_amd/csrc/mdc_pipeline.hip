@@ -540,4 +540,12 @@ int mdc_copy_to_host(mdc_ctx* c, void* dst, const void* d_src, size_t bytes) try
   return MDC_OK;
 } MDC_CATCH(c)
 
+int mdc_copy_to_device(mdc_ctx* c, void* d_dst, const void* src, size_t bytes) try {
+  if (!c) return mdc_device_count() > 0 ? MDC_ERR_ARG : MDC_ERR_NO_DEVICE;
+  if (bytes && (!d_dst || !src)) return fail(c, MDC_ERR_ARG, "mdc_copy_to_device: bad argument");
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, hipMemcpy(d_dst, src, bytes, hipMemcpyDefault));
+  return MDC_OK;
+} MDC_CATCH(c)
+
 }  // extern "C"

@@ -1,0 +1,267 @@
+"""responseCalib on the GPU (include/mdc_hip.h: mdc_rcal_*, DatasetReader::getImagesRawDevice, bin/responseCalib) against the
+test-owned restatement of src/main_responseCalib.cpp (tests/rcal_restatement.py)."""
+import io
+import os
+import subprocess
+import zipfile
+
+import numpy as np
+import pytest
+
+import rcal_restatement as R
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(7, 33, 17, 1), (13, 64, 48, 2), (5, 12, 10, 3), (9, 40, 31, 4)]  # n, w, h, seed: odd widths, w*h < 256, n of no pattern
+
+
+def bits(a):
+    a = np.array(a, np.float64)
+    a[np.isnan(a)] = np.nan  # any NaN payload
+    return a.view(np.uint64)
+
+
+def sweep(n, w, h, seed):
+    rng = np.random.default_rng(seed)
+    stack, t, _ = R.synthetic_sweep(rng, n, w, h, t_lo=0.4, t_hi=40.0, noise=1.5)
+    stack[:, 1, 2] = 255  # a pixel saturated everywhere: E is NaN after the E step
+    return stack, t
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from mono_dataset_code_amd import capi
+
+    return capi.Context(0)
+
+
+def dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+@pytest.mark.parametrize("n,w,h,seed", SIZES)
+def test_steps_equal_the_restatement(ctx, n, w, h, seed):
+    stack, t = sweep(n, w, h, seed)
+    d_stack, d_t = dev(stack), dev(t)
+    ctx.rcal_leak_pad(d_stack, 2)
+    padded = R.leak_pad(stack, w, h, 2)
+    assert np.array_equal(d_stack.cpu().numpy(), padded)
+    E0 = R.init_e(padded)
+    d_E = ctx.rcal_init_e(d_stack)
+    assert np.array_equal(bits(d_E.cpu().numpy()), bits(E0))
+    G0 = np.zeros(256)
+    rm = ctx.rcal_rmse(d_stack, d_t, dev(G0), d_E)
+    want = R.rmse(G0, E0, t, padded)
+    assert rm[1] == want[1] and rm[0] == pytest.approx(want[0], rel=1e-9)
+
+    # G step in the reference's order: bit-identical
+    G1 = R.g_step(E0, t, padded)
+    index = ctx.rcal_index(d_stack)
+    assert index.entries == int((padded != 255).sum())
+    assert index.longest_chain == int(np.bincount(padded[padded != 255].reshape(-1), minlength=256).max())
+    d_G = dev(np.full(256, -1.0))
+    ctx.rcal_g_step_indexed(index, d_t, d_E, d_G)
+    assert np.array_equal(bits(d_G.cpu().numpy()), bits(G1))
+    # direct: deterministic, close
+    d_Gd = dev(np.full(256, -1.0))
+    ctx.rcal_g_step(d_stack, d_t, d_E, d_Gd)
+    Gd = d_Gd.cpu().numpy()
+    d_Gd2 = dev(np.full(256, -1.0))
+    ctx.rcal_g_step(d_stack, d_t, d_E, d_Gd2)
+    assert np.array_equal(bits(Gd), bits(d_Gd2.cpu().numpy()))
+    fin = np.isfinite(G1)
+    assert np.array_equal(fin, np.isfinite(Gd))
+    assert np.max(np.abs(Gd[fin] - G1[fin])) <= 1e-9 * np.max(np.abs(G1[fin]))
+
+    # E step (+ rmse of the new G with the old E): bit-identical
+    E1 = R.e_step(G1, t, padded)
+    rg = ctx.rcal_e_step(d_stack, d_t, d_G, d_E)
+    want = R.rmse(G1, E0, t, padded)
+    assert rg[1] == want[1] and rg[0] == pytest.approx(want[0], rel=1e-9)
+    assert np.array_equal(bits(d_E.cpu().numpy()), bits(E1))
+
+    # rescale: bit-identical, partial on G when w*h < 256
+    G2, E2, _ = R.rescale(G1, E1)
+    before, after = ctx.rcal_rescale(d_stack, d_t, d_G, d_E)
+    assert np.array_equal(bits(d_G.cpu().numpy()), bits(G2))
+    assert np.array_equal(bits(d_E.cpu().numpy()), bits(E2))
+    for got, want in ((before, R.rmse(G1, E1, t, padded)), (after, R.rmse(G2, E2, t, padded))):
+        assert got[1] == want[1] and got[0] == pytest.approx(want[0], rel=1e-9)
+    index.close()
+
+
+@pytest.mark.parametrize("n,w,h,seed", SIZES[:3])
+def test_solve_exact_order_is_bit_identical_after_every_iteration(ctx, n, w, h, seed):
+    from mono_dataset_code_amd import capi
+
+    stack, t = sweep(n, w, h, seed)
+    padded = R.leak_pad(stack, w, h, 2)
+    _, _, ref = R.solve(padded, t, 4)
+    d_stack, d_t = dev(padded), dev(t)
+    for its in (1, 2, 4):
+        G, E, log = ctx.rcal_solve(d_stack, d_t, its, capi.RCAL_EXACT_ORDER)
+        assert np.array_equal(bits(G.cpu().numpy()), bits(ref["G"][its - 1])), its
+        assert np.array_equal(bits(E.cpu().numpy()), bits(ref["E"][its - 1])), its
+        assert log["init_num"] == ref["init"][1] and log["init_rmse"] == pytest.approx(ref["init"][0], rel=1e-9)
+        for k in range(its):
+            for key in ("num_G", "num_E", "num_resc"):
+                assert log["iters"][k][key] == ref["iters"][k][key], (its, k, key)
+            for key in ("rmse_G", "rmse_E", "rmse_resc"):
+                assert log["iters"][k][key] == pytest.approx(ref["iters"][k][key], rel=1e-9), (its, k, key)
+            assert bits([log["iters"][k]["rescale"]]) == bits([ref["iters"][k]["rescale"]])
+
+
+@pytest.mark.parametrize("n,w,h,seed", SIZES[:2])
+def test_solve_direct_is_deterministic_and_close(ctx, n, w, h, seed):
+    from mono_dataset_code_amd import capi
+
+    stack, t = sweep(n, w, h, seed)
+    padded = R.leak_pad(stack, w, h, 2)
+    Gr, Er, _ = R.solve(padded, t, 5)
+    d_stack, d_t = dev(padded), dev(t)
+    G1, E1, _ = ctx.rcal_solve(d_stack, d_t, 5, capi.RCAL_DIRECT)
+    G2, E2, _ = ctx.rcal_solve(d_stack, d_t, 5, capi.RCAL_DIRECT)
+    G1, E1 = G1.cpu().numpy(), E1.cpu().numpy()
+    assert np.array_equal(bits(G1), bits(G2.cpu().numpy())) and np.array_equal(bits(E1), bits(E2.cpu().numpy()))
+    for got, want in ((G1, Gr), (E1, Er)):
+        fin = np.isfinite(want)
+        assert np.array_equal(fin, np.isfinite(got))
+        assert np.max(np.abs(got[fin] - want[fin])) <= 1e-9 * np.max(np.abs(want[fin]))
+
+
+# ---- the reader's raw device frames and the program ----------------------------------------------------------------------
+def encode(img, fmt):
+    b = io.BytesIO()
+    from PIL import Image
+
+    Image.fromarray(img).save(b, {"png": "PNG", "jpg": "JPEG"}[fmt], **({"quality": 90} if fmt == "jpg" else {}))
+    return b.getvalue()
+
+
+def write_sweep(d, blobs, t, zipped, fmt, calibration):
+    os.makedirs(d, exist_ok=True)
+    names = ["%05d.%s" % (i, fmt) for i in range(len(blobs))]
+    if zipped:
+        with zipfile.ZipFile(os.path.join(d, "images.zip"), "w") as z:
+            for nm, b in zip(names, blobs):
+                z.writestr(nm, b)
+    else:
+        os.makedirs(os.path.join(d, "images"))
+        for nm, b in zip(names, blobs):
+            open(os.path.join(d, "images", nm), "wb").write(b)
+    with open(os.path.join(d, "times.txt"), "w") as f:
+        for i, ti in enumerate(t):
+            f.write("%d %.6f %.9g\n" % (i, 1000.0 + i / 20.0, ti))
+    if calibration:
+        from mono_dataset_code_amd import synth
+
+        h, w = calibration
+        cam = ("0.349153 0.436593 0.493140 0.499021 0.933271", "%d %d" % (w, h), "crop", "%d %d" % (w * 3 // 5, h * 9 // 16))
+        synth.write_sequence_calibration(d, cam, vignette_bits=16, n_times=0)
+        with open(os.path.join(d, "times.txt"), "w") as f:  # (write_sequence_calibration leaves times.txt alone with n_times=0)
+            for i, ti in enumerate(t):
+                f.write("%d %.6f %.9g\n" % (i, 1000.0 + i / 20.0, ti))
+    return names
+
+
+@pytest.mark.parametrize("zipped,fmt,calib", [(False, "png", True), (True, "png", False), (False, "jpg", False), (True, "jpg", True)])
+def test_raw_device_frames_equal_get_image_raw(tmp_path, zipped, fmt, calib):
+    import torch
+
+    from mono_dataset_code_amd import capi
+
+    w, h = 48, 36
+    stack, t = sweep(11, w, h, 5)
+    blobs = [encode(f, fmt) for f in stack]
+    blobs[3] = b"not an image at all"                            # undecodable
+    blobs[6] = encode(np.zeros((h + 2, w), np.uint8) + 7, fmt)   # wrong size
+    d = str(tmp_path / "seq")
+    write_sweep(d, blobs, t, zipped, fmt, (h, w) if calib else None)
+    r = capi.DatasetReader(d)
+    assert r.raw_dims() == (w, h)
+    for first, count, step in ((0, 11, 1), (1, 5, 2), (2, 4, 3), (9, 4, 1)):
+        out = torch.full((count, h * w), 99, dtype=torch.uint8, device="cuda")
+        valid, got = r.get_images_raw_device(first, count, step, out)
+        host = out.cpu().numpy()
+        for j in range(count):
+            fid = first + j * step
+            ok = fid < 11 and fid not in (3, 6)
+            assert valid[j] == ok, (first, step, j)
+            if ok:
+                want = r.get_raw(fid) if calib else None
+                if want is not None:
+                    assert np.array_equal(host[j], want.reshape(-1))
+                if fmt == "png":
+                    assert np.array_equal(host[j], stack[fid].reshape(-1))
+            else:
+                assert np.all(host[j] == 99)
+        assert got == int(valid.sum())
+    r.close()
+
+
+def parse_tokens(path):
+    return open(path).read().split()
+
+
+def same_token(a, b):
+    if a.lstrip("-") == "nan" and b.lstrip("-") == "nan":
+        return True
+    return a == b
+
+
+@pytest.mark.parametrize("order", ["exact", "direct"])
+def test_response_calib_program_end_to_end(tmp_path, order):
+    from mono_dataset_code_amd import build, capi
+
+    w, h, n = 64, 48, 60
+    # exposures from 1e-4 on: the darkest frames populate bins 0 and 1, and 60 of them make the result strictly increasing -- a
+    # gamma PhotometricUndistorter accepts
+    stack, t, _ = R.synthetic_sweep(np.random.default_rng(21), n, w, h, t_lo=1e-4, t_hi=40.0, noise=1.0)
+    t32 = t.astype(np.float32).astype(np.float64)  # times.txt -> getExposure is a float (:202)
+    d = str(tmp_path / "sweep")
+    write_sweep(d, [encode(f, "png") for f in stack], t32, zipped=False, fmt="png", calibration=None)
+    run = tmp_path / "run"
+    run.mkdir()
+    args = [build.RESPONSE_CALIB, d, "iterations=6", "order=" + order]
+    p = subprocess.run(args, cwd=str(run), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "nits set to 6!" in p.stdout and "loaded %d images" % n in p.stdout and "resc RMSE = " in p.stdout
+    padded = R.leak_pad(stack, w, h, 2)
+    G, E, log = R.solve(padded, t32, 6)
+    got = parse_tokens(run / "photoCalibResult" / "pcalib.txt")
+    want = R.pcalib_text(G).split()
+    assert len(got) == 256
+    if order == "exact":
+        assert all(same_token(a, b) for a, b in zip(got, want)), [(a, b) for a, b in zip(got, want) if not same_token(a, b)][:5]
+    else:
+        g = np.array([float(x) for x in got])
+        fin = np.isfinite(G)
+        assert np.max(np.abs(g[fin] - G[fin])) <= 1e-9 * np.max(np.abs(G[fin]))
+    rows = [line.split() for line in open(run / "photoCalibResult" / "log.txt")]
+    assert len(rows) == 6
+    for k, row in enumerate(rows):
+        assert int(row[0]) == k and int(row[1]) == n and float(row[2]) == log["iters"][k]["num_resc"]
+        assert float(row[3]) == pytest.approx(log["iters"][k]["rmse_resc"], rel=1e-9)
+    # the result is a gamma PhotometricUndistorter accepts (monotonic, bins 0 and 1 populated by the sweep)
+    if order == "exact":
+        from mono_dataset_code_amd import synth
+
+        synth.write_png_gray(str(tmp_path / "v.png"), np.full((h, w), 255, np.uint8))
+        ph = capi.PhotometricUndistorter(str(run / "photoCalibResult" / "pcalib.txt"), str(tmp_path / "v.png"), w, h)
+        assert ph.valid() & 1
+
+
+def test_response_calib_program_size_mismatch(tmp_path):
+    from mono_dataset_code_amd import build
+
+    w, h = 40, 30
+    stack, t = sweep(5, w, h, 8)
+    blobs = [encode(f, "png") for f in stack]
+    blobs[2] = encode(np.zeros((h, w + 4), np.uint8), "png")
+    d = str(tmp_path / "sweep")
+    write_sweep(d, blobs, t, zipped=False, fmt="png", calibration=None)
+    p = subprocess.run([build.RESPONSE_CALIB, d], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode == 1 and "width mismatch!" in p.stdout
+    assert not os.path.exists(tmp_path / "photoCalibResult")
