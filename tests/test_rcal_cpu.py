@@ -212,3 +212,58 @@ def test_program_is_built():
     from mono_dataset_code_amd import build
 
     assert os.access(build.RESPONSE_CALIB, os.X_OK)
+
+
+# ---- the large-stack forms of the restatement (tests/test_rcal_sizes.py) against the plain ones ----------------------------
+def sparse_stack(rng, n, w, h, listed):
+    """a stack that is 255 except at `listed` random positions -> (stack, positions in a shuffled order, their bytes)"""
+    pos = rng.choice(n * w * h, listed, replace=False)
+    vals = rng.integers(0, 255, listed).astype(np.uint8)
+    stack = np.full(n * w * h, 255, np.uint8)
+    stack[pos] = vals
+    return stack.reshape(n, h, w), pos, vals
+
+
+def wide_range(rng, size, lo=-8.0, hi=8.0):
+    return 10.0 ** rng.uniform(lo, hi, size)
+
+
+@pytest.mark.parametrize("n,w,h,listed,seed", [(5, 9, 7, 200, 1), (3, 31, 17, 900, 2), (12, 16, 16, 40, 3), (1, 300, 1, 299, 4)])
+def test_sparse_forms_equal_the_plain_ones(n, w, h, listed, seed):
+    rng = np.random.default_rng(seed)
+    stack, pos, vals = sparse_stack(rng, n, w, h, listed)
+    t = wide_range(rng, n, -3, 3)
+    E = wide_range(rng, w * h)
+    E[rng.random(w * h) < 0.05] = np.nan
+    assert np.array_equal(bits(R.init_e_sparse(pos, vals, n, w * h)), bits(R.init_e(stack)))
+    G = R.g_step(E, t, stack)
+    assert np.array_equal(bits(R.g_step_sparse(pos, vals, E, t, w * h)), bits(G))
+    G[rng.random(256) < 0.1] = np.nan
+    assert np.array_equal(bits(R.e_step_sparse(pos, vals, G, t, w * h)), bits(R.e_step(G, t, stack)))
+    E2 = R.e_step(G, t, stack)
+    for g, e in ((G, E), (G, E2)):
+        got, want = R.rmse_sparse(pos, vals, g, e, t, w * h), R.rmse(g, e, t, stack)
+        assert got[1] == want[1] and bits([got[0]]) == bits([want[0]])
+
+
+@pytest.mark.parametrize("n,w,h,seed", [(4, 6, 5, 1), (9, 33, 17, 2), (2, 256, 3, 3)])
+def test_g_step_by_image_equals_g_step(n, w, h, seed):
+    rng = np.random.default_rng(seed)
+    stack = tiny_stack(rng, n, w, h)
+    t = wide_range(rng, n, -3, 3)
+    E = wide_range(rng, w * h)
+    E[0] = np.nan
+    assert np.array_equal(bits(R.g_step_by_image(E, t, stack)), bits(R.g_step(E, t, stack)))
+    _, _, a = R.solve(stack, t, 2)
+    _, _, b = R.solve(stack, t, 2, g=R.g_step_by_image)
+    for it in range(2):
+        assert np.array_equal(bits(a["G"][it]), bits(b["G"][it])) and np.array_equal(bits(a["E"][it]), bits(b["E"][it]))
+        assert a["iters"][it] == b["iters"][it]
+
+
+def test_sparse_g_step_sees_the_order():
+    """The forms above would not notice a reordered sum if every order gave the same bits: on these products it does not."""
+    rng = np.random.default_rng(5)
+    prod = wide_range(rng, 1537)
+    seq = np.cumsum(np.concatenate([[0.0], prod]))[-1]
+    assert seq != np.cumsum(prod[::-1])[-1] and seq != np.sum(prod) and seq != math.fsum(prod)
