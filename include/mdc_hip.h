@@ -436,6 +436,13 @@ MDC_API int mdc_distort_points_host(mdc_ctx* ctx, const mdc_fov_model* model, fl
 
 /* ---- vignetteCalib solver (src/main_vignetteCalib.cpp:395-527) ----------------------------------- */
 
+/* Size limits (MDC_ERR_ARG past them; tests/test_vcal_sizes.py runs each entry point at and past its own):
+ *   w * h < 2^31                  plane step, both vignette steps, index, solve, gradient mask, smoothing (int pixel indices)
+ *   n_images <= 65535             atomic vignette step, index, solve, image scaling (one launch, grid y = image)
+ *   n_plane < 2^30                index, solve (an entry packs plane point | corner << 30)
+ * The plane step takes any n_images >= 0 and n_plane < 2^31, the coordinate mask any int64 n; stack offsets are 64-bit
+ * everywhere, so a stack may exceed 2^32 bytes. */
+
 /* One "optimize planeColor" half-iteration (:400-448) over n_images images of w x h floats (stacked in d_images,
  * NaN = masked pixel, :294-300) seen through the plane -> image coordinates d_p2x / d_p2y (n_images x n_plane, NaN =
  * plane point outside that image, after distortCoordinates, :284): for every plane point the sums FF, FC over the

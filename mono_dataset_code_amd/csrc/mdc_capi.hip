@@ -822,7 +822,7 @@ int mdc_vcal_plane_step_device(mdc_ctx* c, const float* d_images, const float* d
                                float* d_fc, double* d_er, void* stream) try {
   if (!c) return MDC_ERR_ARG;
   if (!d_images || !d_p2x || !d_p2y || !d_plane_color || !d_vignette_factor || !d_ff || !d_fc || !d_er || n_images < 0 || w < 2 ||
-      h < 2 || n_plane < 0)
+      h < 2 || n_plane < 0 || (long long)w * h >= (1ll << 31))  // int pixel indices in the kernel
     return fail(c, MDC_ERR_ARG, "mdc_vcal_plane_step_device: bad argument");
   ReadLock lk(c->mu);
   DeviceGuard dg(c->device);
@@ -835,8 +835,8 @@ int mdc_vcal_vignette_step_device(mdc_ctx* c, const float* d_images, const float
                                   int h, int n_plane, const float* d_plane_color, float* d_vignette_factor, int oth2, float* d_tt,
                                   float* d_ct, double* d_er, void* stream) try {
   if (!c) return MDC_ERR_ARG;
-  if (!d_images || !d_p2x || !d_p2y || !d_plane_color || !d_vignette_factor || !d_tt || !d_ct || !d_er || n_images < 0 || w < 2 ||
-      h < 2 || n_plane < 0)
+  if (!d_images || !d_p2x || !d_p2y || !d_plane_color || !d_vignette_factor || !d_tt || !d_ct || !d_er || n_images < 0 ||
+      n_images > 65535 || w < 2 || h < 2 || n_plane < 0 || (long long)w * h >= (1ll << 31))  // grid y = n_images; int pixel indices
     return fail(c, MDC_ERR_ARG, "mdc_vcal_vignette_step_device: bad argument");
   ReadLock lk(c->mu);
   DeviceGuard dg(c->device);

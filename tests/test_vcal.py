@@ -10,6 +10,7 @@ GPU : mdc_vcal_plane_step == oracle bit for bit (each plane point sums over the 
 import numpy as np
 import pytest
 
+import vcal_problems as P
 from conftest import bits_equal
 
 
@@ -118,8 +119,8 @@ def test_gpu_indexed_vignette_step_is_bit_identical(oracle):
         n, hI, wI = images.shape
         d_img, d_x, d_y = (torch.from_numpy(a).cuda() for a in (images, p2x, p2y))
         index = ctx.vcal_index(d_img, d_x, d_y, st)
-        valid = ~np.isnan(p2x) & ~np.isnan(p2y) & (p2x < wI - 1) & (p2y < hI - 1)
-        assert 0 < index.entries <= 4 * int(valid.sum()) and index.bytes >= 16 * index.entries
+        valid = P.listed(images, p2x, p2y)[0]  # coordinate present, footprint inside, four colour taps non-NaN
+        assert 0 < index.entries == 4 * int(valid.sum()) and index.bytes >= 16 * index.entries
         if seed == 2:
             p2x[3, 17] = p2x[4, 18] = np.nan  # what the oracle sees: the same samples masked by the caller
         pc = np.zeros(gw * gh, np.float32)
