@@ -513,6 +513,21 @@ MDC_API int mdc_vcal_gradient_mask_device(mdc_ctx* ctx, float* d_images, int n_i
  * leave the device. */
 MDC_API int mdc_vcal_mask_coords_device(mdc_ctx* ctx, float* d_x, float* d_y, int64_t n, int w, int h, void* stream);
 
+/* The plane -> image coordinates of n calibration frames (:230-258, :284, :345-357), written straight into the solver's
+ * d_p2x / d_p2y (n x gw*gh floats each, frame-major, plane point x + y * gw).  gw, gh, facw, fach are the reference's patternX,
+ * patternY, facW, facH (defaults 1000, 1000, 5, 5).
+ *   d_corners != NULL: n x 4 corners (x, y) in the rectified frame, in aruco's order -- the images of the plane points
+ *     (-0.5, 0.5), (0.5, 0.5), (0.5, -0.5), (-0.5, -0.5) (:246-253).  Per frame H is the exact 4-point homography in double,
+ *     scaled to H(2,2) = 1 (cv::findHomography's fit of 4 points lands on the same map up to its last bits), and
+ *     HK = float(H) * K_p2idx^-1 in float with Eigen's (>= 3.3) expressions; HK is written to d_hk (n x 9 floats, row-major).
+ *   d_corners == NULL: HK is read from d_hk -- for a caller with a detector or homography of its own.
+ * Then per plane point pp = HK * (x, y, 1) and (pp0 / pp2, pp1 / pp2) in the reference's float order (no contraction), through
+ * the camera's distortCoordinates (the bits of mdc_distort_points_device) and the rule of mdc_vcal_mask_coords_device with the
+ * model's input size: equal, bit for bit, to those two calls after the projection.  model == NULL: the projection only.
+ * Corners 1, 2, 3 on a line give a non-finite HK (NaN coordinates), other collinear triples a singular one.  Limits: n <= 65535 (grid y), gw * gh < 2^31. */
+MDC_API int mdc_vcal_plane_coords_device(mdc_ctx* ctx, const mdc_fov_model* model, const float* d_corners, float* d_hk, int n, int gw,
+                                 int gh, float facw, float fach, float* d_p2x, float* d_p2y, void* stream);
+
 /* "dilate & smoothe vignette by 4 pixel for output" (:541-566): four passes of a NaN-aware 3 x 3 mean over the w x h
  * factor map (what the reference writes as vignetteSmoothed.png, i.e. the vignette image PhotometricUndistorter reads).
  * d_smoothed (result) and d_scratch are w*h floats each, distinct from each other; d_vignette_factor is not modified and

@@ -40,6 +40,7 @@ HIP_SYMBOLS = [
     "mdc_vcal_vignette_step_device", "mdc_gradients_batch_device", "mdc_process_pyramid_gradients_batch_device", "mdc_tune_device",
     "mdc_vcal_index_create", "mdc_vcal_index_destroy", "mdc_vcal_index_bytes", "mdc_vcal_index_entries",
     "mdc_vcal_vignette_step_indexed_device", "mdc_vcal_solve_device", "mdc_vcal_smooth_device", "mdc_vcal_mask_coords_device", "mdc_vcal_gradient_mask_device", "mdc_vcal_scale_images_device",
+    "mdc_vcal_plane_coords_device",
     "mdc_rcal_leak_pad_device", "mdc_rcal_init_e_device", "mdc_rcal_rmse_device", "mdc_rcal_g_step_device", "mdc_rcal_index_create",
     "mdc_rcal_index_destroy", "mdc_rcal_index_bytes", "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain",
     "mdc_rcal_g_step_indexed_device", "mdc_rcal_e_step_device", "mdc_rcal_rescale_device", "mdc_rcal_solve_device", "mdc_copy_to_device",
@@ -271,6 +272,8 @@ def hip_lib():
             L.mdc_vcal_mask_coords_device.argtypes = [_vp, _vp, _vp, C.c_int64, _i, _i, _vp]
             L.mdc_vcal_gradient_mask_device.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
             L.mdc_vcal_scale_images_device.argtypes = [_vp, _vp, _i, C.c_int64, C.c_float, _vp, _vp]
+        if not old_build or hasattr(L, "mdc_vcal_plane_coords_device"):
+            L.mdc_vcal_plane_coords_device.argtypes = [_vp, C.POINTER(FovModel), _vp, _vp, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]
         if not old_build or hasattr(L, "mdc_rcal_solve_device"):
             L.mdc_rcal_leak_pad_device.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
             L.mdc_rcal_init_e_device.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
@@ -744,6 +747,27 @@ class Context:
     def vcal_mask_coords(self, d_x, d_y, w, h, stream=0):
         """NaN coordinates for plane points outside the w x h image (src/main_vignetteCalib.cpp:345-357), in place."""
         self._chk(self._L.mdc_vcal_mask_coords_device(self._h, d_x.data_ptr(), d_y.data_ptr(), d_x.numel(), w, h, stream if stream else None))
+
+    def vcal_plane_coords(self, model, gw, gh, facw=5.0, fach=5.0, corners=None, hk=None, stream=0):
+        """Plane -> image coordinates of n frames (src/main_vignetteCalib.cpp:230-258, :284, :345-357) -> (p2x, p2y, hk): device
+        tensors (n, gw*gh), (n, gw*gh), (n, 3, 3).  corners: (n, 4, 2) float32 device tensor in aruco's corner order (HK is fitted
+        from them), or hk: (n, 3, 3) float32 device tensor given as is.  model: FovModel (distortion and coordinate mask) or None
+        (the projection only)."""
+        import torch
+
+        assert (corners is None) != (hk is None)
+        src = corners if hk is None else hk
+        n = src.shape[0]
+        if hk is None:
+            assert corners.dtype == torch.float32 and corners.is_contiguous() and tuple(corners.shape[1:]) == (4, 2)
+            hk = torch.empty((n, 3, 3), dtype=torch.float32, device=corners.device)
+        assert hk.dtype == torch.float32 and hk.is_contiguous() and tuple(hk.shape) == (n, 3, 3)
+        p2x = torch.empty((n, gw * gh), dtype=torch.float32, device=src.device)
+        p2y = torch.empty_like(p2x)
+        self._chk(self._L.mdc_vcal_plane_coords_device(self._h, C.byref(model) if model is not None else None,
+                                                       corners.data_ptr() if corners is not None else None, hk.data_ptr(), n, gw, gh,
+                                                       float(facw), float(fach), p2x.data_ptr(), p2y.data_ptr(), stream if stream else None))
+        return p2x, p2y, hk
 
     def vcal_smooth(self, d_vig, w, h, stream=0):
         """vignetteCalib's output smoothing (src/main_vignetteCalib.cpp:541-566) -> (smoothed, scratch) device tensors."""

@@ -919,6 +919,21 @@ int mdc_vcal_mask_coords_device(mdc_ctx* c, float* d_x, float* d_y, int64_t n, i
   return MDC_OK;
 } MDC_CATCH(c)
 
+int mdc_vcal_plane_coords_device(mdc_ctx* c, const mdc_fov_model* model, const float* d_corners, float* d_hk, int n, int gw, int gh,
+                                 float facw, float fach, float* d_p2x, float* d_p2y, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (n < 0 || n > 65535 || gw < 1 || gh < 1 || (long long)gw * gh >= (1ll << 31) ||
+      (n > 0 && (!d_hk || !d_p2x || !d_p2y)) || (model && (model->in_w < 1 || model->in_h < 1)))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_plane_coords_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  DistortModel m;
+  if (model) m = distort_model(model);
+  MDC_HIP(c, launch_vcal_plane_coords(d_corners, d_hk, n, gw, gh, facw, fach, model ? &m : nullptr, model ? model->in_w : 0,
+                                      model ? model->in_h : 0, d_p2x, d_p2y, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
 int mdc_vcal_smooth_device(mdc_ctx* c, const float* d_vignette_factor, int w, int h, float* d_smoothed, float* d_scratch,
                            void* stream) try {
   if (!c) return MDC_ERR_ARG;

@@ -146,6 +146,10 @@ hipError_t launch_vcal_scale_images(float* d_images, int n, int64_t npix, float 
 hipError_t launch_vcal_gradient_mask(float* d_images, int n, int wI, int hI, int max_abs_grad, hipStream_t s);
 // vignetteCalib: NaN coordinates for plane points outside the image (:345-357)
 hipError_t launch_vcal_mask_coords(float* d_x, float* d_y, int64_t n, int wI, int hI, hipStream_t s);
+// vignetteCalib: plane -> image coordinates of n frames (:230-258, :284, :345-357); d_corners (n x 8) -> d_hk (n x 9) first when
+// given; m == nullptr: the projection only
+hipError_t launch_vcal_plane_coords(const float* d_corners, float* d_hk, int n, int gw, int gh, float facw, float fach,
+                                    const DistortModel* m, int wI, int hI, float* d_p2x, float* d_p2y, hipStream_t s);
 // vignetteCalib's output smoothing (:541-566): four NaN-aware 3 x 3 mean passes; d_tt = result, d_ct = scratch
 hipError_t launch_vcal_smooth(const float* d_vig, int wI, int hI, float* d_tt, float* d_ct, hipStream_t s);
 

@@ -423,15 +423,85 @@ __global__ __launch_bounds__(256) void vcal_gradient_mask_kernel(float* __restri
 // :345-357: plane points whose image position, rounded as (int)(v + 0.5) (float + double), is not strictly inside
 // (1, w-2) x (1, h-2) lose both coordinates.  (NaN / out-of-range conversions saturate here and give INT_MIN on the
 // reference's x86 -- either way the test fails and the point is masked.)
+__device__ __forceinline__ bool vcal_coord_inside(float x, float y, int wI, int hI) {
+  const int u_d = (int)(x + 0.5);
+  const int v_d = (int)(y + 0.5);
+  return u_d > 1 && v_d > 1 && u_d < wI - 2 && v_d < hI - 2;
+}
+
 __global__ __launch_bounds__(256) void vcal_mask_coords_kernel(float* __restrict__ x, float* __restrict__ y, long long n, int wI, int hI) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const int u_d = (int)(x[i] + 0.5);
-  const int v_d = (int)(y[i] + 0.5);
-  if (!(u_d > 1 && v_d > 1 && u_d < wI - 2 && v_d < hI - 2)) {
+  if (!vcal_coord_inside(x[i], y[i], wI, hI)) {
     x[i] = __builtin_nanf("");
     y[i] = __builtin_nanf("");
   }
+}
+
+// :230-258: one lane per frame turns the marker's 4 corners into HK = float(H) * K_p2idx^-1.  H maps the plane points
+// (-0.5, 0.5), (0.5, 0.5), (0.5, -0.5), (-0.5, -0.5) onto the corners exactly: for 4 points the DLT's solution is the
+// square-to-quad map (Heckbert 1989), formed here in double and scaled to H(2,2) = 1 as cv::findHomography leaves it.
+// K_p2idx^-1 and the product are Eigen's float expressions (>= 3.3): the 3 x 3 inverse as cofactors times 1 / det, a
+// coefficient of a product as a0 + (a1 + a2).  Corners 1, 2, 3 on a line give a non-finite HK, other degenerate quads a singular one.
+__global__ __launch_bounds__(64) void vcal_plane_homography_kernel(const float* __restrict__ corners, float* __restrict__ hk, int n,
+                                                                   int gw, int gh, float facw, float fach) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= n) return;
+  const float* c = corners + (long long)f * 8;
+  const double x0 = c[0], y0 = c[1], x1 = c[2], y1 = c[3], x2 = c[4], y2 = c[5], x3 = c[6], y3 = c[7];
+  const double sx = x0 - x1 + x2 - x3, sy = y0 - y1 + y2 - y3;
+  const double dx1 = x1 - x2, dx2 = x3 - x2, dy1 = y1 - y2, dy2 = y3 - y2;
+  const double det = dx1 * dy2 - dx2 * dy1;
+  const double g = (sx * dy2 - dx2 * sy) / det, h = (dx1 * sy - sx * dy1) / det;
+  // unit square (u, v) -> image: columns q0 (u), q1 (v), q2 (1); the plane point (X, Y) is (u, v) = (X + 0.5, 0.5 - Y)
+  const double q0[3] = {x1 - x0 + g * x1, y1 - y0 + g * y1, g};
+  const double q1[3] = {x3 - x0 + h * x3, y3 - y0 + h * y3, h};
+  const double q2[3] = {x0, y0, 1.0};
+  const double s = 1.0 / (0.5 * g + 0.5 * h + 1.0);
+  float H[3][3];
+  for (int i = 0; i < 3; i++) {
+    H[i][0] = (float)(q0[i] * s);
+    H[i][1] = (float)(-q1[i] * s);
+    H[i][2] = (float)((0.5 * q0[i] + 0.5 * q1[i] + q2[i]) * s);
+  }
+  // K_p2idx (:193-197; gw / 2 is an int division) and Eigen's compute_inverse<3>
+  const float K[3][3] = {{gw / facw, 0.f, (float)(gw / 2)}, {0.f, gh / fach, (float)(gh / 2)}, {0.f, 0.f, 1.f}};
+  float cof[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      cof[i][j] = K[i1][j1] * K[i2][j2] - K[i1][j2] * K[i2][j1];
+    }
+  const float kdet = cof[0][0] * K[0][0] + (cof[1][0] * K[1][0] + cof[2][0] * K[2][0]);
+  const float invdet = 1.0f / kdet;
+  float* o = hk + (long long)f * 9;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++)  // Kinv(k, j) = cof(j, k) * invdet
+      o[i * 3 + j] = H[i][0] * (cof[j][0] * invdet) + (H[i][1] * (cof[j][1] * invdet) + H[i][2] * (cof[j][2] * invdet));
+}
+
+// :246-258, :284, :345-357 in one pass: frame blockIdx.y, plane point idx = x + y * gw; pp = HK * (x, y, 1) in Eigen's
+// order, u = pp0 / pp2, v = pp1 / pp2, then (with a lens model) distortCoordinates and the coordinate mask of
+// vcal_mask_coords_kernel, written straight into the solver's p2x / p2y rows.
+template <bool DISTORT>
+__global__ __launch_bounds__(256) void vcal_plane_coords_kernel(const float* __restrict__ hk, int gw, int np, DistortModel m, int wI,
+                                                                int hI, float* __restrict__ p2x, float* __restrict__ p2y) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= np) return;
+  const float* K = hk + (long long)blockIdx.y * 9;
+  const int y = idx / gw, x = idx - y * gw;
+  const float fx = (float)x, fy = (float)y;
+  const float pp0 = K[0] * fx + (K[1] * fy + K[2] * 1.0f);
+  const float pp1 = K[3] * fx + (K[4] * fy + K[5] * 1.0f);
+  const float pp2 = K[6] * fx + (K[7] * fy + K[8] * 1.0f);
+  float u = pp0 / pp2, v = pp1 / pp2;
+  if (DISTORT) {
+    fov_distort_point(m, u, v);
+    if (!vcal_coord_inside(u, v, wI, hI)) u = v = __builtin_nanf("");
+  }
+  const long long o = (long long)blockIdx.y * np + idx;
+  p2x[o] = u;
+  p2y[o] = v;
 }
 
 // "dilate & smoothe vignette by 4 pixel for output" (:541-566): one pass of the NaN-aware 3 x 3 mean, src -> dst; the nine
@@ -710,6 +780,18 @@ hipError_t launch_vcal_gradient_mask(float* d_images, int n, int wI, int hI, int
 hipError_t launch_vcal_mask_coords(float* d_x, float* d_y, int64_t n, int wI, int hI, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   vcal_mask_coords_kernel<<<blocks(n), 256, 0, s>>>(d_x, d_y, n, wI, hI);
+  return hipGetLastError();
+}
+
+hipError_t launch_vcal_plane_coords(const float* d_corners, float* d_hk, int n, int gw, int gh, float facw, float fach,
+                                    const DistortModel* m, int wI, int hI, float* d_p2x, float* d_p2y, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (d_corners) vcal_plane_homography_kernel<<<(n + 63) / 64, 64, 0, s>>>(d_corners, d_hk, n, gw, gh, facw, fach);
+  const int np = gw * gh;
+  if (m)
+    vcal_plane_coords_kernel<true><<<dim3(blocks(np), n), 256, 0, s>>>(d_hk, gw, np, *m, wI, hI, d_p2x, d_p2y);
+  else
+    vcal_plane_coords_kernel<false><<<dim3(blocks(np), n), 256, 0, s>>>(d_hk, gw, np, DistortModel{}, 0, 0, d_p2x, d_p2y);
   return hipGetLastError();
 }
 
