@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the photometric + FOV undistortion hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--full]
                   [--workload fused|unmap|pyramid|seq50k]
 
 One "step" = one pass of the hot path over one batch of B synthetic 1280x1024 u8
@@ -18,9 +18,16 @@ Rank 0 prints ONE JSON line: BASELINE.json's metric (Mpix/s of input pixels,
 whole job), plus
   roofline     : algorithmic HBM bytes per launch / launch duration (HIP events on the
                  launching stream; mean is the contract's figure, median and min beside
-                 it) against the 8 TB/s HBM peak, AND against this box's own ceiling for
-                 the same byte counts (a linear read+write stream timed in this process:
-                 boxes differ by +-5 %, the ratio does not);
+                 it) against the 8 TB/s HBM peak.
+
+A plain run does only what the headline needs: set-up (tables, the allocator's buffers, the
+tuner's plan), pre-roll and warm-up, the timed steps, --dump-outputs, the line.  --full adds
+what takes runs or checks of its own, after the headline's timed steps:
+  roofline     : ... AND against this box's own ceiling for the same byte counts (a linear
+                 read+write stream timed in this process: boxes differ by +-5 %, the ratio
+                 does not);
+  parity       : spot frames of the timed launch against the oracle / the reference build;
+  secondary    : the other BASELINE.json configs, then the headline timed again (again);
   cpu_baseline : the reference's own CPU path (oracle/_ref) on a bounded sample of the
                  same frames, timed on this box: all host cores (value), one thread (the
                  reference as shipped), and unMapImage alone (N=1 only).
@@ -92,8 +99,11 @@ def parse():
                         "allocations as they come, malloc = candidates + every pair timed, vmm = ranges assembled from classified physical pieces")
     p.add_argument("--placement-candidates", type=int, default=0,
                    help="malloc strategy: candidate allocations per buffer (0 = the library's default, 6; 1 = same as --placement first)")
-    p.add_argument("--no-again", action="store_true", help="do not time the headline a second time after the secondary workloads")
-    p.add_argument("--parity-frames", type=int, default=16, help="frames of the benchmarked launch compared with the oracle")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps, also: its same-box ceiling, spot parity against the oracle, the other configs "
+                        "(secondary) and the headline again, the CPU reference.  Off: the headline alone")
+    p.add_argument("--no-again", action="store_true", help="--full: do not time the headline a second time after the secondary workloads")
+    p.add_argument("--parity-frames", type=int, default=16, help="--full: frames of the benchmarked launch compared with the oracle")
     p.add_argument("--frames", type=int, default=0,
                    help="frames per GPU per step = batch of one launch (0 = 4096 for fused/unmap, 1024 for pyramid; "
                         "seq50k: the rank's shard)")
@@ -106,16 +116,16 @@ def parse():
     p.add_argument("--two-stage", type=int, default=0, choices=[0, 1, 2], help="wave-private strip kernel: 0 = library's choice, 1 = wherever plannable, 2 = off")
     p.add_argument("--no-tune", action="store_true", help="keep the library's built-in tile shape / frames per workgroup instead "
                                                           "of mdc_tune_device's measured choice (untimed, before the warm-up)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU reference")
     p.add_argument("--no-secondary", action="store_true",
-                   help="only the headline workload (default: after it, the other BASELINE.json configs are timed for "
+                   help="--full: only the headline workload (else, after it, the other BASELINE.json configs are timed for "
                         "--secondary-steps steps each and reported under \"secondary\" in the same line)")
     p.add_argument("--secondary-steps", type=int, default=20)
-    p.add_argument("--no-ceiling", action="store_true", help="skip the same-box linear-mix ceiling")
+    p.add_argument("--no-ceiling", action="store_true", help="--full: skip the same-box linear-mix ceiling")
     p.add_argument("--markers", action="store_true",
                    help="bracket the headline's timed region with two launches of a no-op kernel (mdcb_marker_kernel, libmdc_bench.so) outside the timed "
                         "wall-clock region, on the stream of the timed launches: tools/profile_round.py cuts rocprofv3's trace / counters to the launches between them")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU time of the all-core baseline sample")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: target CPU time of the all-core baseline sample")
     p.add_argument("--dump-dir", default="", help="test hook: every rank writes its first --dump-frames outputs here")
     p.add_argument("--dump-frames", type=int, default=0)
     p.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -911,7 +921,8 @@ class Workload:
 
 
 def measure(W, steps, warmup, do_ceiling, parity_frames, min_preroll=None, dump=False):
-    """pre-roll to a steady state, time, (rank 0:) yardstick + spot parity -> the workload's result dictionary on rank 0, None elsewhere"""
+    """pre-roll to a steady state, time, (rank 0:) yardstick + spot parity (parity_frames None: none) -> the workload's result
+    dictionary on rank 0, None elsewhere"""
     pre = W.preroll(min_preroll)
     timing = W.timed(steps, warmup)
     if dump:
@@ -921,7 +932,8 @@ def measure(W, steps, warmup, do_ceiling, parity_frames, min_preroll=None, dump=
     if W.D.rank != 0:
         return None
     ceiling = W.ceiling() if do_ceiling else None
-    return W.result(timing, ceiling, W.parity(parity_frames), pre)
+    parity = W.parity(parity_frames) if parity_frames is not None else "not checked (bench.py --full compares the launch with the oracle)"
+    return W.result(timing, ceiling, parity, pre)
 
 
 def main():
@@ -933,10 +945,10 @@ def main():
     from mono_dataset_code_amd import capi
 
     wl = args.workload
-    do_ceiling = not args.no_ceiling
+    do_ceiling = args.full and not args.no_ceiling
     clocks_idle = gpu_clock_snapshot(D.gpu)
     H = Workload(args, D, wl, args.frames)
-    head = measure(H, args.steps, args.warmup, do_ceiling, args.parity_frames, dump=True)
+    head = measure(H, args.steps, args.warmup, do_ceiling, args.parity_frames if args.full else None, dump=True)
     # every rank's buffers come from the product's allocator; its probe times (median of 5 launches of the pass over min(B, 4096) frames, on the
     # built-in plan) on the pair it handed out and on the first two plain allocations of the device, per rank
     place_all = D.gather([float(H.placed.ms_first), float(H.placed.ms_chosen), float(H.placed.strategy)])
@@ -952,11 +964,11 @@ def main():
     for d_, pl in zip(devices, place_all):
         d_["placement"] = {"strategy": capi.PLACE_NAMES.get(int(pl[2]), "?"), "probe_ms_on_first_allocations": round(pl[0], 4) or None,
                            "probe_ms_on_chosen_pair": round(pl[1], 4) or None}
-    # ---- the other BASELINE.json configs, timed in the same process (same box, same clocks) -------------------------
+    # ---- --full: the other BASELINE.json configs, timed in the same process (same box, same clocks) -----------------
     # N = 1: configs[1] unMapImage, configs[4] pyramid, configs[3] as one 50,000-frame sequence on the one GPU.
     # N > 1: configs[3] as BASELINE.json words it -- the one sequence dealt round-robin over the ranks (strong scaling).
     secondary = None
-    if wl == "fused" and not args.no_secondary and not args.frames:
+    if args.full and wl == "fused" and not args.no_secondary and not args.frames:
         secondary = {}
         todo = ("unmap", "undistort_f32", "pyramid", "dso", "seq50k") if D.world == 1 else ("seq50k",)
         for w2 in todo:
@@ -1006,7 +1018,7 @@ def main():
             out["roofline"]["frac_again_over_frac"] = round(again["frac"] / max(out["roofline"]["frac"], 1e-9), 4)
         if secondary is not None:
             out["secondary"] = secondary
-        if D.world == 1 and not args.no_cpu_baseline:
+        if args.full and D.world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, H.calib_dir, H.rect)
         print(json.dumps(out), flush=True)
     if D.active:

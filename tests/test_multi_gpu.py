@@ -140,7 +140,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, oracle):
     shard, barrier + max-over-ranks timing, one JSON line from rank 0) with two ranks sharing the one GPU
     of the test box: gloo carries the collectives there (RCCL wants one device per rank).  EVERY rank's first
     three outputs are compared with the oracle for their global frame indices."""
-    out = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2",
+    out = _bench(["--full", "--gpus", "2", "--steps", "5", "--warmup", "2", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2",
                   "--dump-dir", str(tmp_path), "--dump-frames", "3"], env={"MDC_BENCH_BACKEND": "gloo"}, nproc=2)
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 5
     assert out["config"]["frames_per_gpu_per_step"] == 64 and "cpu_baseline" not in out
@@ -158,7 +158,7 @@ def test_bench_launches_its_own_ranks(tmp_path, oracle):
     import torch
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    out = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--dump-dir", str(tmp_path),
+    out = _bench(["--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--dump-dir", str(tmp_path),
                   "--dump-frames", "2"], env=dict(env, MDC_BENCH_BACKEND="gloo"), clean_env=True)
     assert out["n_gpus"] == 2 and out["ranks"]["world"] == 2 and out["ranks"]["backend"] == "gloo"
     assert [d["rank"] for d in out["ranks"]["devices"]] == [0, 1]
@@ -179,7 +179,7 @@ def test_bench_launches_its_own_ranks(tmp_path, oracle):
 def test_bench_seq50k_sharding_two_ranks(tmp_path, oracle):
     """BASELINE.json configs[3] (one sequence, frame f on GPU f % N), shrunk to 2 x 40 frames: strong scaling line,
     per-rank outputs equal to the oracle for the global indices."""
-    out = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "seq50k", "--frames", "40", "--preroll-s", "0.05", "--preroll-max-s", "0.2",
+    out = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "seq50k", "--frames", "40", "--preroll-s", "0.05", "--preroll-max-s", "0.2",
                   "--dump-dir", str(tmp_path), "--dump-frames", "2", "--no-ceiling"], env={"MDC_BENCH_BACKEND": "gloo"}, nproc=2, port=29537)
     assert out["scaling"] == "strong" and out["config"]["sequence_frames"] == 80 and out["config"]["frames_per_gpu_per_step"] == 40
     assert out["parity"]["mismatching_pixels"] == 0
@@ -190,7 +190,7 @@ def test_bench_seq50k_sharding_two_ranks(tmp_path, oracle):
 def test_bench_rccl_branch_executes_with_a_world_of_one(tmp_path):
     """The "nccl" (= RCCL) branch of bench.py on the one GPU of the test box: process-group init on the device, the
     table broadcast, the barriers and the all-reduce / all-gather all run through RCCL with world size 1."""
-    out = _bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--frames", "128", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline"],
+    out = _bench(["--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--frames", "128", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline"],
                  env={"MDC_BENCH_FORCE_DIST": "1", "MDC_BENCH_BACKEND": "nccl", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0",
                       "MASTER_PORT": "29539"})
     assert out["n_gpus"] == 1 and out["config"]["collective_backend"] == "nccl"
@@ -204,7 +204,7 @@ def test_bench_rccl_branch_executes_with_a_world_of_one(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_pyramid_checks_every_level():
-    out = _bench(["--steps", "3", "--warmup", "1", "--workload", "pyramid", "--frames", "16", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline"])
+    out = _bench(["--full", "--steps", "3", "--warmup", "1", "--workload", "pyramid", "--frames", "16", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline"])
     par = out["parity"]
     assert (par["frames_checked"], par["levels_checked"], par["mismatching_pixels"]) == (16, 4, 0)  # --frames 16: every frame of the launch
     # base against the reference build where it was built (else the C oracle, pinned to the reference's recorded answers); the levels' definition is ours
@@ -229,7 +229,7 @@ def test_bench_over_rccl_on_real_devices(tmp_path, oracle):
     for n in sorted({2, ndev}):
         dump = tmp_path / ("dump%d" % n)
         dump.mkdir()
-        out = _bench(["--gpus", str(n), "--steps", "5", "--warmup", "2", "--frames", "256", "--preroll-s", "0.05", "--preroll-max-s", "0.3",
+        out = _bench(["--full", "--gpus", str(n), "--steps", "5", "--warmup", "2", "--frames", "256", "--preroll-s", "0.05", "--preroll-max-s", "0.3",
                       "--dump-dir", str(dump), "--dump-frames", "3", "--no-cpu-baseline"], clean_env=False, timeout=1200)
         ranks = out["ranks"]
         assert out["n_gpus"] == n and ranks["world"] == n and ranks["backend"] == "nccl" and ranks["rccl_ranks"] == n
@@ -241,7 +241,7 @@ def test_bench_over_rccl_on_real_devices(tmp_path, oracle):
         for d_ in ranks["devices"]:
             assert d_["placement"]["strategy"] in ("first", "malloc", "vmm"), d_
         _check_rank_dumps(str(dump), n, 3, oracle)
-        seq = _bench(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--workload", "seq50k", "--frames", "96", "--preroll-s", "0.05", "--preroll-max-s",
+        seq = _bench(["--full", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--workload", "seq50k", "--frames", "96", "--preroll-s", "0.05", "--preroll-max-s",
                       "0.3", "--no-cpu-baseline"], timeout=1200)
         assert seq["scaling"] == "strong" and seq["config"]["sequence_frames"] == 96 * n and seq["parity"]["mismatching_pixels"] == 0
         assert seq["ranks"]["rccl_ranks"] == n and len(seq["roofline"]["per_rank_frac"]) == n
@@ -253,7 +253,7 @@ def test_bench_takes_its_buffers_from_the_product_allocator(strategy):
     """bench.py has no buffer search of its own: frames and results come from mdc_alloc_placed_device (libmdc_hip.so), whose report -- the
     strategy, what it timed, the probe on the first allocations beside the probe on the pair handed out -- goes into the line."""
     env = {"MDC_PLACE_SPREAD_MB": "2000", "MDC_PLACE_PIECE_MIB": "256"}
-    out = _bench(["--steps", "4", "--warmup", "1", "--frames", "1024", "--placement", strategy, "--placement-candidates", "3", "--preroll-s", "0.05",
+    out = _bench(["--full", "--steps", "4", "--warmup", "1", "--frames", "1024", "--placement", strategy, "--placement-candidates", "3", "--preroll-s", "0.05",
                   "--preroll-max-s", "0.3", "--no-cpu-baseline", "--no-secondary"], env=env)
     pl = out["config"]["placement"]
     assert pl["strategy"] == strategy and pl["probe_frames"] == 1024 and pl["ms_on_chosen_pair"] > 0
@@ -271,9 +271,23 @@ def test_bench_takes_its_buffers_from_the_product_allocator(strategy):
         assert 0.2 < rp["frac_on_first_allocation"] < 0.9
     assert out["ranks"]["devices"][0]["placement"]["strategy"] == strategy
     assert 0.2 < out["roofline"]["frac"] < 0.9
-    plain = _bench(["--steps", "4", "--warmup", "1", "--frames", "1024", "--placement", "first", "--preroll-s", "0.05", "--preroll-max-s", "0.3",
+    plain = _bench(["--full", "--steps", "4", "--warmup", "1", "--frames", "1024", "--placement", "first", "--preroll-s", "0.05", "--preroll-max-s", "0.3",
                     "--no-cpu-baseline", "--no-secondary"])
     assert plain["config"]["placement"]["strategy"] == "first" and plain["parity"]["mismatching_pixels"] == 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full the line carries the headline and nothing that takes runs or checks of its own -- no same-box ceiling, no parity,
+    no other configs, no second timing, no CPU reference --, on the headline's own batch of 4096 frames, where --full adds them all."""
+    out = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--preroll-s", "0.05", "--preroll-max-s", "0.3"])
+    assert (out["metric"], out["unit"], out["higher_is_better"], out["dtype"]) == ("Mpix/s photometric+FOV undistort, 1280x1024 gray", "Mpix/s", True, "f32")
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["config"]["frames_per_gpu_per_step"] == 4096
+    assert out["value"] == pytest.approx(4096 * 1280 * 1024 / 1e6 / (out["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not {"secondary", "again", "cpu_baseline"} & set(out), sorted(out)
+    assert not {"same_box_mix_ceiling", "frac_of_same_box_mix_ceiling", "frac_again"} & set(out["roofline"])
+    assert isinstance(out["parity"], str) and "--full" in out["parity"]
+    assert out["roofline"]["kernel"].startswith("remap_tiled_kernel<") and 0.2 < out["roofline"]["frac"] < 0.9
 
 
 def _dump_check(dump_dir, workload, world, oracle, stride=None):
@@ -315,7 +329,7 @@ def _dump_check(dump_dir, workload, world, oracle, stride=None):
 @pytest.mark.gpu
 def test_bench_dump_outputs_repeat_and_match_the_oracle(tmp_path, oracle):
     """Two runs of the headline with the same arguments write the same files, byte for byte, and the sampled frames are the oracle's."""
-    args = ["--steps", "3", "--warmup", "1", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline", "--no-ceiling"]
+    args = ["--full", "--steps", "3", "--warmup", "1", "--frames", "64", "--preroll-s", "0.05", "--preroll-max-s", "0.2", "--no-cpu-baseline", "--no-ceiling"]
     dumps = []
     for run in ("a", "b"):
         out = _bench(args + ["--dump-outputs", str(tmp_path / run)])

@@ -11,7 +11,7 @@
 #                    over tools/mall_bracket.py (one launch per variant)
 #   pmc_sq           SQ / TCC / TCP counter passes over tools/sweep.py (PMC_ARGS="--shapes 128x16 --fpb 64")
 #   launch_size      bench.py --frames 4096 / 8192 / 16384 (headline only)
-#   bench            plain `python bench.py` (the driver's command) -> bench.json
+#   bench            `python bench.py --full` (the headline, its ceiling and parity, the other configs, the CPU reference) -> bench.json
 #   pyramid_alone    bench.py --workload pyramid in its own process (against the secondary entry of `bench`)
 #   bench2           `python bench.py --gpus 2` without torchrun (gloo, shared GPU)
 #   profile          tools/profile_round.py: rocprofv3 --kernel-trace --stats + FETCH_SIZE / WRITE_SIZE passes of bench.py's workloads, cut to the timed region
@@ -65,7 +65,7 @@ for stage in "$@"; do
       python3 tools/pmc_table.py "$OUT" sq_pass > "$OUT/sq_summary.txt" 2>&1; tail -8 "$OUT/sq_summary.txt" ;;
     launch_size)
       for n in 4096 8192 16384; do
-        timeout 300 python bench.py --frames $n --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/bench_frames_$n.json" 2> "$OUT/bench_frames_$n.err"
+        timeout 300 python bench.py --full --frames $n --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/bench_frames_$n.json" 2> "$OUT/bench_frames_$n.err"
         python3 -c "import json,sys; d=json.loads([l for l in open('$OUT/bench_frames_$n.json') if l.startswith('{')][-1]); r=d['roofline']; print($n, 'frac', r['frac'], 'kernel_ms', r['kernel_ms'], 'of_ceiling', r.get('frac_of_same_box_mix_ceiling'), r['kernel'], d['config']['plan'])"
       done ;;
     ab)      # same-box A/B of library builds / knobs on the headline batch: tools/sweep.py with AB_ARGS (interleaved rounds, outputs compared bit for bit)
@@ -90,7 +90,7 @@ for stage in "$@"; do
       timeout 300 python tools/clock_probe.py ${PROBE_ARGS:-12 4 3} > "$OUT/clock_probe.txt" 2>&1; grep -a "===\|^A \|^B \|plan:\|idle snapshot" -A0 "$OUT/clock_probe.txt" | tail -8 ;;
     bench_each)  # every workload in its own process (which one faults?)
       for wl in fused unmap pyramid dso seq50k; do
-        timeout 300 python3 bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > "$OUT/bench_each_$wl.json" 2> "$OUT/bench_each_$wl.err"; echo "$wl rc=$?"
+        timeout 300 python3 bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > "$OUT/bench_each_$wl.json" 2> "$OUT/bench_each_$wl.err"; echo "$wl rc=$?"
         tail -c 300 "$OUT/bench_each_$wl.err" | grep -a "fault\|Error\|error" ; python3 -c "
 import json,sys
 try:
@@ -112,7 +112,7 @@ for k, v in (d.get("secondary") or {}).items():
 PY
       ;;
     bench)
-      ( time timeout 1200 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ) 2>&1 | grep real; tail -c 600 "$OUT/bench.err"
+      ( time timeout 1200 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ) 2>&1 | grep real; tail -c 600 "$OUT/bench.err"
       python3 - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -124,7 +124,7 @@ print("cpu_baseline", {k: d.get("cpu_baseline", {}).get(k) for k in ("value", "c
 PY
       ;;
     pyramid_alone)
-      for i in 1 2; do timeout 300 python bench.py --workload pyramid --no-cpu-baseline > "$OUT/bench_pyramid_alone_$i.json" 2> /dev/null
+      for i in 1 2; do timeout 300 python bench.py --full --workload pyramid --no-cpu-baseline > "$OUT/bench_pyramid_alone_$i.json" 2> /dev/null
         python3 -c "import json; d=json.loads([l for l in open('$OUT/bench_pyramid_alone_$i.json') if l.startswith('{')][-1]); r=d['roofline']; print('pyramid alone: frac', r['frac'], 'kernel_ms', r['kernel_ms'], 'of ceiling', r.get('frac_of_same_box_mix_ceiling'), r.get('launches_per_step'))"; done ;;
     bench2)
       MDC_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 20 --warmup 3 > "$OUT/bench_gpus2_gloo.json" 2> "$OUT/bench_gpus2_gloo.err"; echo "rc=$?"

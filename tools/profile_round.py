@@ -74,7 +74,7 @@ def main():
         shutil.rmtree(scratch, ignore_errors=True)
         os.makedirs(scratch)
         bench = ["python3", os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps", str(steps), "--warmup", "5", "--no-cpu-baseline", "--no-ceiling",
-                 "--no-secondary", "--markers", "--parity-frames", "2"]
+                 "--no-secondary", "--markers", "--parity-frames", "2", "--full"]  # --full: the line's spot parity goes into the summary
         if shape:
             bench += ["--tile-cols", shape.split("x")[0], "--tile-rows", shape.split("x")[1], "--fpb", "128"]
         base = os.path.join(outdir, "%s_%s" % (tag, name))
