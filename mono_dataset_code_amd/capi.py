@@ -7,6 +7,7 @@ there is no Python or CPU fallback for the per-frame work.
 """
 import ctypes as C
 import os
+import types
 
 import numpy as np
 
@@ -26,37 +27,6 @@ OPT_TAIL_TAPER = 15
 OPT_DEVICE_PIPELINE_CHUNK, OPT_DEVICE_PIPELINE_CHUNK_HINT = 16, 17
 ORDER_BANDS, ORDER_ROWS, ORDER_IDENTITY, ORDER_BLOCKS2D = 0, 1, 2, 3
 OK, ERR_ARG, ERR_STATE, ERR_SIZE, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
-
-# every symbol include/mdc_hip.h declares (checked by tests/test_abi.py)
-HIP_SYMBOLS = [
-    "mdc_create", "mdc_destroy", "mdc_device_count", "mdc_device_pci_bus_id", "mdc_last_error", "mdc_build_flags", "mdc_code_id", "mdc_get_info", "mdc_set_option", "mdc_set_photometric",
-    "mdc_set_remap", "mdc_unmap_host", "mdc_undistort_host_f32", "mdc_undistort_host_u8", "mdc_process_host",
-    "mdc_process_frames_host_to_device", "mdc_process_jpeg_frames_host_to_device", "mdc_process_jpeg_streams_host_to_device", "mdc_device_alloc", "mdc_tune_placement_device", "mdc_alloc_placed_device", "mdc_free_placed_device", "mdc_alloc_striped_set_device", "mdc_free_striped_set_device", "mdc_device_free", "mdc_copy_to_host",
-    "mdc_host_alloc", "mdc_host_free", "mdc_process_frames_host", "mdc_process_jpeg_frames_host", "mdc_jpeg_idct_batch_device", "mdc_process_jpeg_streams_host", "mdc_jpeg_huffman_batch_device",
-    "mdc_unmap_batch_device", "mdc_process_batch_device", "mdc_undistort_batch_device_f32",
-    "mdc_pyramid_batch_device", "mdc_process_pyramid_batch_device",
-    "mdc_distort_points_device", "mdc_distort_points_host", "mdc_export_tables", "mdc_import_tables",
-    "mdc_synchronize", "mdc_describe_launch", "mdc_vcal_plane_step_device",
-    "mdc_vcal_vignette_step_device", "mdc_gradients_batch_device", "mdc_process_pyramid_gradients_batch_device", "mdc_tune_device",
-    "mdc_vcal_index_create", "mdc_vcal_index_destroy", "mdc_vcal_index_bytes", "mdc_vcal_index_entries",
-    "mdc_vcal_vignette_step_indexed_device", "mdc_vcal_solve_device", "mdc_vcal_smooth_device", "mdc_vcal_mask_coords_device", "mdc_vcal_gradient_mask_device", "mdc_vcal_scale_images_device",
-    "mdc_vcal_plane_coords_device",
-    "mdc_rcal_leak_pad_device", "mdc_rcal_init_e_device", "mdc_rcal_rmse_device", "mdc_rcal_g_step_device", "mdc_rcal_index_create",
-    "mdc_rcal_index_destroy", "mdc_rcal_index_bytes", "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain",
-    "mdc_rcal_g_step_indexed_device", "mdc_rcal_e_step_device", "mdc_rcal_rescale_device", "mdc_rcal_solve_device", "mdc_copy_to_device",
-]
-HOST_SYMBOLS = [
-    "mdch_fov_create", "mdch_fov_destroy", "mdch_fov_valid", "mdch_fov_has_gpu", "mdch_fov_dims",
-    "mdch_fov_intrinsics", "mdch_fov_model", "mdch_fov_remap", "mdch_fov_distort", "mdch_fov_undistort_f32", "mdch_fov_undistort_u8",
-    "mdch_photo_create", "mdch_photo_destroy", "mdch_photo_valid", "mdch_photo_has_gpu", "mdch_photo_ginv",
-    "mdch_photo_g", "mdch_photo_vignette", "mdch_photo_unmap", "mdch_bind", "mdch_pack_tables",
-    "mdch_reader_create", "mdch_reader_destroy", "mdch_reader_num_images", "mdch_reader_timestamp", "mdch_reader_exposure",
-    "mdch_reader_dims", "mdch_reader_get_image", "mdch_reader_get_images", "mdch_reader_get_images_device", "mdch_reader_context", "mdch_reader_device", "mdch_reader_get_raw", "mdch_reader_set_threads",
-    "mdch_reader_set_prefetch", "mdch_reader_set_gpu_jpeg", "mdch_reader_set_lookahead", "mdch_reader_last_error", "mdch_reader_prefetch_stats", "mdch_reader_device_stats", "mdch_decode_gray8", "mdch_jpeg_record_bytes",
-    "mdch_decode_jpeg_record", "mdch_jpeg_stream", "mdch_image_alloc", "mdch_image_free",
-    "mdch_image_pool_trim", "mdch_image_pool_idle_bytes", "mdch_reader_get_images_raw_device", "mdch_reader_raw_dims",
-]
-
 
 PLACE_AUTO, PLACE_FIRST, PLACE_MALLOC, PLACE_VMM = 0, 1, 2, 3
 PLACE_NAMES = {PLACE_AUTO: "auto", PLACE_FIRST: "first", PLACE_MALLOC: "malloc", PLACE_VMM: "vmm"}
@@ -143,9 +113,170 @@ class MdcError(RuntimeError):
         self.code = code
 
 
+_vp, _i, _i64, _u32, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_size_t
+_u, _f, _cp, _P = C.c_uint, C.c_float, C.c_char_p, C.POINTER
+
+# The signatures, name -> (restype, argtypes): the one place an entry point is declared on the Python side, one row each, in
+# the order and under the section comments of its header.  tests/test_abi.py checks every row against the header's declaration.
+HIP_API = {  # include/mdc_hip.h (libmdc_hip.so)
+    # ---- lifetime
+    "mdc_create": (_i, [_i, _P(_vp)]),
+    "mdc_device_count": (_i, []),
+    "mdc_device_pci_bus_id": (_i, [_vp, _cp, _sz]),
+    "mdc_destroy": (None, [_vp]),
+    "mdc_last_error": (_cp, [_vp]),
+    "mdc_get_info": (_i, [_vp, _P(MdcInfo)]),
+    "mdc_set_option": (_i, [_vp, _i, _i]),
+    "mdc_build_flags": (_cp, []),
+    "mdc_code_id": (_cp, []),
+    # ---- calibration tables (once per sequence)
+    "mdc_set_photometric": (_i, [_vp, _vp, _vp, _i, _i]),
+    "mdc_set_remap": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    # ---- host-pointer, single-frame
+    "mdc_unmap_host": (_i, [_vp, _vp, _vp, _i, _u]),
+    "mdc_undistort_host_f32": (_i, [_vp, _vp, _vp, _i, _i]),
+    "mdc_undistort_host_u8": (_i, [_vp, _vp, _vp, _i, _i]),
+    "mdc_process_host": (_i, [_vp, _vp, _vp, _u]),
+    # ---- host-pointer, many frames
+    "mdc_host_alloc": (_vp, [_sz]),
+    "mdc_host_free": (None, [_vp]),
+    "mdc_process_frames_host": (_i, [_vp, _P(_vp), _P(_vp), _i64, _u]),
+    "mdc_process_jpeg_frames_host": (_i, [_vp, _P(_vp), _i64, _i, _i, _P(_vp), _i64, _u]),
+    "mdc_jpeg_idct_batch_device": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _i64, _vp]),
+    "mdc_process_jpeg_streams_host": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp), _i64, _u, _P(_i)]),
+    "mdc_jpeg_huffman_batch_device": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i64, _vp, _vp]),
+    # ---- host frames in, results left on the device
+    "mdc_process_frames_host_to_device": (_i, [_vp, _P(_vp), _i64, _u, _P(DeviceOutputs), _P(_i64)]),
+    "mdc_process_jpeg_frames_host_to_device": (_i, [_vp, _P(_vp), _i64, _i, _i, _i64, _u, _P(DeviceOutputs), _P(_i64)]),
+    "mdc_process_jpeg_streams_host_to_device": (_i, [_vp, _P(_vp), _P(_i64), _i64, _u, _P(DeviceOutputs), _P(_i64), _P(_i)]),
+    "mdc_device_alloc": (_i, [_vp, _sz, _P(_vp)]),
+    "mdc_tune_placement_device": (_i, [_vp, _P(_vp), _i, _P(_vp), _i, _i64, _u, _vp, _P(_i), _P(_i), _P(_f)]),
+    "mdc_alloc_placed_device": (_i, [_vp, _sz, _sz, _i64, _u, _i, _vp, _P(PlacedBuffers)]),
+    "mdc_free_placed_device": (_i, [_vp, _P(PlacedBuffers)]),
+    "mdc_alloc_striped_set_device": (_i, [_vp, _i, _P(_sz), _vp, _P(StripedSet)]),
+    "mdc_free_striped_set_device": (_i, [_vp, _P(StripedSet)]),
+    "mdc_device_free": (None, [_vp, _vp]),
+    "mdc_copy_to_host": (_i, [_vp, _vp, _vp, _sz]),
+    # ---- device-pointer, batched: the throughput path
+    "mdc_unmap_batch_device": (_i, [_vp, _vp, _vp, _i64, _u, _vp]),
+    "mdc_process_batch_device": (_i, [_vp, _vp, _vp, _i64, _u, _vp]),
+    "mdc_undistort_batch_device_f32": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "mdc_pyramid_batch_device": (_i, [_vp, _vp, _i, _i, _i, _P(_vp), _i64, _vp]),
+    "mdc_process_pyramid_batch_device": (_i, [_vp, _vp, _vp, _i, _P(_vp), _i64, _u, _vp]),
+    "mdc_gradients_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _vp]),
+    "mdc_process_pyramid_gradients_batch_device": (_i, [_vp, _vp, _vp, _i, _P(_vp), _P(_vp), _P(_vp), _i64, _u, _i, _vp]),
+    # ---- lens model on many points
+    "mdc_distort_points_device": (_i, [_vp, _P(FovModel), _vp, _vp, _i64, _vp]),
+    "mdc_distort_points_host": (_i, [_vp, _P(FovModel), _vp, _vp, _i64]),
+    # ---- vignetteCalib solver
+    "mdc_vcal_plane_step_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mdc_vcal_vignette_step_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mdc_vcal_index_create": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _P(_vp)]),
+    "mdc_vcal_index_destroy": (None, [_vp]),
+    "mdc_vcal_index_bytes": (_i64, [_vp]),
+    "mdc_vcal_index_entries": (_i64, [_vp]),
+    "mdc_vcal_vignette_step_indexed_device": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mdc_vcal_solve_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "mdc_vcal_scale_images_device": (_i, [_vp, _vp, _i, _i64, _f, _vp, _vp]),
+    "mdc_vcal_gradient_mask_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mdc_vcal_mask_coords_device": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "mdc_vcal_plane_coords_device": (_i, [_vp, _P(FovModel), _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "mdc_vcal_smooth_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    # ---- responseCalib solver
+    "mdc_rcal_leak_pad_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mdc_rcal_init_e_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mdc_rcal_rmse_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mdc_rcal_g_step_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mdc_rcal_index_create": (_i, [_vp, _vp, _i, _i, _i, _vp, _P(_vp)]),
+    "mdc_rcal_index_destroy": (None, [_vp]),
+    "mdc_rcal_index_bytes": (_i64, [_vp]),
+    "mdc_rcal_index_entries": (_i64, [_vp]),
+    "mdc_rcal_index_longest_chain": (_i64, [_vp]),
+    "mdc_rcal_g_step_indexed_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mdc_rcal_e_step_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mdc_rcal_rescale_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mdc_rcal_solve_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _u, _vp, _vp, _P(RcalLog), _vp]),
+    "mdc_copy_to_device": (_i, [_vp, _vp, _vp, _sz]),
+    # ---- plan selection by measurement, diagnostics
+    "mdc_tune_device": (_i, [_vp, _vp, _vp, _i64, _u, _vp, _P(TuneResult)]),
+    "mdc_describe_launch": (_i, [_vp, _u, _i, _cp, _sz]),
+    # ---- calibration hand-over between ranks (multi-GPU)
+    "mdc_export_tables": (_i, [_vp, _vp, _sz, _P(_sz)]),
+    "mdc_import_tables": (_i, [_vp, _vp, _sz]),
+    "mdc_synchronize": (_i, [_vp]),
+}
+HOST_API = {  # include/mdc_host.h (libmdc_host.so)
+    # ---- class UndistorterFOV
+    "mdch_fov_create": (_vp, [_cp]),
+    "mdch_fov_destroy": (None, [_vp]),
+    "mdch_fov_valid": (_i, [_vp]),
+    "mdch_fov_has_gpu": (_i, [_vp]),
+    "mdch_fov_dims": (None, [_vp, _vp]),
+    "mdch_fov_intrinsics": (None, [_vp, _vp]),
+    "mdch_fov_remap": (_i, [_vp, _vp, _vp]),
+    "mdch_fov_distort": (None, [_vp, _vp, _vp, _i]),
+    "mdch_fov_undistort_f32": (None, [_vp, _vp, _vp, _i, _i]),
+    "mdch_fov_undistort_u8": (None, [_vp, _vp, _vp, _i, _i]),
+    "mdch_fov_model": (None, [_vp, _P(FovModel)]),
+    # ---- class PhotometricUndistorter
+    "mdch_photo_create": (_vp, [_cp, _cp, _i, _i]),
+    "mdch_photo_destroy": (None, [_vp]),
+    "mdch_photo_valid": (_i, [_vp]),
+    "mdch_photo_has_gpu": (_i, [_vp]),
+    "mdch_photo_ginv": (_i, [_vp, _vp]),
+    "mdch_photo_g": (_i, [_vp, _vp]),
+    "mdch_photo_vignette": (_i, [_vp, _vp, _vp]),
+    "mdch_photo_unmap": (None, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    # ---- tables of the two objects into a GPU context / a blob
+    "mdch_bind": (_i, [_vp, _vp, _vp]),
+    "mdch_pack_tables": (_i, [_vp, _vp, _vp, _sz, _P(_sz)]),
+    # ---- class DatasetReader
+    "mdch_reader_create": (_vp, [_cp]),
+    "mdch_reader_destroy": (None, [_vp]),
+    "mdch_reader_num_images": (_i, [_vp]),
+    "mdch_reader_timestamp": (C.c_double, [_vp, _i]),
+    "mdch_reader_exposure": (_f, [_vp, _i]),
+    "mdch_reader_dims": (None, [_vp, _vp]),
+    "mdch_reader_get_image": (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, _P(C.c_double), _P(_f)]),
+    "mdch_reader_get_images": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_long, _vp]),
+    "mdch_reader_get_images_device": (_i, [_vp, _i, _i, _i, _i, _i, _i, _P(DeviceOutputs), _vp]),
+    "mdch_reader_context": (_vp, [_vp]),
+    "mdch_reader_device": (_i, [_vp]),
+    "mdch_reader_get_raw": (_i, [_vp, _i, _vp, C.c_long, _vp]),
+    "mdch_reader_get_images_raw_device": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mdch_reader_raw_dims": (None, [_vp, _vp]),
+    "mdch_reader_set_threads": (None, [_vp, _i]),
+    "mdch_reader_set_prefetch": (None, [_vp, _i]),
+    "mdch_reader_set_lookahead": (None, [_vp, _i]),
+    "mdch_reader_set_gpu_jpeg": (None, [_vp, _i]),
+    "mdch_reader_last_error": (_cp, [_vp]),
+    "mdch_reader_prefetch_stats": (None, [_vp, _vp]),
+    "mdch_reader_device_stats": (_i, [_vp, _i, _vp, _vp]),
+    # ---- the reader's frame decoders on a byte string
+    "mdch_decode_gray8": (_i, [_vp, _sz, _vp, _sz, _vp, _cp, _sz]),
+    "mdch_jpeg_record_bytes": (_sz, [_i, _i, _vp]),
+    "mdch_decode_jpeg_record": (_i, [_vp, _sz, _vp, _sz, _i, _vp, _cp, _sz]),
+    "mdch_jpeg_stream": (C.c_longlong, [_vp, _sz, _vp, _sz, _vp, _cp, _sz]),
+    # ---- ExposureImage's pixel pool
+    "mdch_image_alloc": (_vp, [C.c_ulong]),
+    "mdch_image_free": (None, [_vp]),
+    "mdch_image_pool_trim": (None, []),
+    "mdch_image_pool_idle_bytes": (C.c_ulong, []),
+}
+BENCH_API = {  # include/mdc_bench.h (libmdc_bench.so; not the product ABI)
+    "mdcb_synth_frames_device": (_i, [_i, _vp, _i64, _i64, _i, _u32, _vp]),
+    "mdcb_ceiling_mix_device": (_i, [_i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
+    "mdcb_marker_device": (_i, [_i, _i, _vp]),
+    "mdcb_alias_alloc": (_i, [_i, _i64, _i, _P(_vp), _P(_i64)]),
+    "mdcb_alias_free": (_i, [_i, _vp, _i64, _i]),
+    "mdcb_chunked_alloc": (_i, [_i, _i64, _i, _i, _P(_vp)]),
+}
+HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
+
+LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
 _hip = None
 _host = None
-_vp, _i, _i64, _u32, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_size_t
+_bench = None
 
 
 def _share_hip_runtime_with_torch():
@@ -160,9 +291,27 @@ def _share_hip_runtime_with_torch():
         pass
 
 
-LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
-BENCH_SYMBOLS = ["mdcb_synth_frames_device", "mdcb_ceiling_mix_device", "mdcb_alias_alloc", "mdcb_alias_free", "mdcb_chunked_alloc", "mdcb_marker_device"]  # include/mdc_bench.h (not the product ABI)
-_bench = None
+def _bind(lib, table, product):
+    """The functions of `table` on the loaded library `lib`, each with its restype / argtypes set, as a namespace that holds
+    nothing else: a function the table does not declare cannot be called through it (ctypes would marshal its arguments as C
+    int).  product: `lib` is the in-tree build, which must have every entry; another build of libmdc_hip (MDC_LIB_HIP, a module
+    copy with LIB_HIP_PATH reassigned) may predate some, and those are left out, so that using one raises AttributeError."""
+    ns = types.SimpleNamespace()
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            if product:
+                raise OSError("%s does not export %s: rebuild with `python -m mono_dataset_code_amd.build`" % (getattr(lib, "_name", lib), name))
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
+        setattr(ns, name, fn)
+    return ns
+
+
+def _load(path, table, product=True):
+    if not os.path.exists(path):
+        raise OSError("%s not built: run `python -m mono_dataset_code_amd.build`" % path)
+    return _bind(C.CDLL(path), table, product)
 
 
 def bench_lib():
@@ -170,16 +319,7 @@ def bench_lib():
     global _bench
     if _bench is None:
         _share_hip_runtime_with_torch()
-        if not os.path.exists(LIB_BENCH_PATH):
-            raise OSError("%s not built: run `python -m mono_dataset_code_amd.build`" % LIB_BENCH_PATH)
-        L = C.CDLL(LIB_BENCH_PATH)
-        L.mdcb_synth_frames_device.argtypes = [_i, _vp, _i64, _i64, _i, _u32, _vp]
-        L.mdcb_ceiling_mix_device.argtypes = [_i, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _vp]
-        L.mdcb_alias_alloc.argtypes = [_i, C.c_int64, _i, C.POINTER(_vp), C.POINTER(C.c_int64)]
-        L.mdcb_alias_free.argtypes = [_i, _vp, C.c_int64, _i]
-        L.mdcb_chunked_alloc.argtypes = [_i, C.c_int64, _i, _i, C.POINTER(_vp)]
-        L.mdcb_marker_device.argtypes = [_i, _i, _vp]
-        _bench = L
+        _bench = _load(LIB_BENCH_PATH, BENCH_API)
     return _bench
 
 
@@ -187,117 +327,8 @@ def hip_lib():
     global _hip
     if _hip is None:
         _share_hip_runtime_with_torch()
-        if not os.path.exists(LIB_HIP_PATH):
-            raise OSError("%s not built: run `python -m mono_dataset_code_amd.build`" % LIB_HIP_PATH)
-        L = C.CDLL(LIB_HIP_PATH)
-        L.mdc_create.argtypes = [_i, C.POINTER(_vp)]
-        L.mdc_destroy.argtypes = [_vp]
-        L.mdc_destroy.restype = None
-        L.mdc_last_error.argtypes = [_vp]
-        L.mdc_last_error.restype = C.c_char_p
-        if hasattr(L, "mdc_build_flags"):  # (absent from libraries built before round 4: tools/sweep.py --libs)
-            L.mdc_build_flags.argtypes = []
-            L.mdc_build_flags.restype = C.c_char_p
-        if hasattr(L, "mdc_code_id"):  # (absent from libraries built before round 5)
-            L.mdc_code_id.argtypes = []
-            L.mdc_code_id.restype = C.c_char_p
-        L.mdc_get_info.argtypes = [_vp, C.POINTER(MdcInfo)]
-        L.mdc_set_option.argtypes = [_vp, _i, _i]
-        L.mdc_set_photometric.argtypes = [_vp, _vp, _vp, _i, _i]
-        L.mdc_set_remap.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i]
-        L.mdc_unmap_host.argtypes = [_vp, _vp, _vp, _i, C.c_uint]
-        L.mdc_undistort_host_f32.argtypes = [_vp, _vp, _vp, _i, _i]
-        L.mdc_undistort_host_u8.argtypes = [_vp, _vp, _vp, _i, _i]
-        L.mdc_process_host.argtypes = [_vp, _vp, _vp, C.c_uint]
-        L.mdc_host_alloc.argtypes = [_sz]
-        L.mdc_host_alloc.restype = _vp
-        L.mdc_host_free.argtypes = [_vp]
-        L.mdc_host_free.restype = None
-        L.mdc_process_frames_host.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp), _i64, C.c_uint]
-        if hasattr(L, "mdc_process_jpeg_frames_host"):
-            L.mdc_process_jpeg_frames_host.argtypes = [_vp, C.POINTER(_vp), _i64, _i, _i, C.POINTER(_vp), _i64, C.c_uint]
-            L.mdc_jpeg_idct_batch_device.argtypes = [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _i64, _vp]
-            L.mdc_process_jpeg_streams_host.argtypes = [_vp, C.POINTER(_vp), C.POINTER(C.c_int64), C.POINTER(_vp), _i64, C.c_uint, C.POINTER(C.c_int)]
-            L.mdc_jpeg_huffman_batch_device.argtypes = [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i64, _vp, _vp]
-        if hasattr(L, "mdc_process_jpeg_streams_host_to_device"):  # (absent from libraries built before round 5)
-            L.mdc_process_frames_host_to_device.argtypes = [_vp, C.POINTER(_vp), _i64, C.c_uint, C.POINTER(DeviceOutputs), C.POINTER(C.c_int64)]
-            L.mdc_process_jpeg_frames_host_to_device.argtypes = [_vp, C.POINTER(_vp), _i64, _i, _i, _i64, C.c_uint, C.POINTER(DeviceOutputs), C.POINTER(C.c_int64)]
-            L.mdc_process_jpeg_streams_host_to_device.argtypes = [_vp, C.POINTER(_vp), C.POINTER(C.c_int64), _i64, C.c_uint, C.POINTER(DeviceOutputs),
-                                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int)]
-            L.mdc_device_alloc.argtypes = [_vp, _sz, C.POINTER(_vp)]
-            L.mdc_tune_placement_device.argtypes = [_vp, C.POINTER(_vp), _i, C.POINTER(_vp), _i, _i64, C.c_uint, _vp, C.POINTER(_i), C.POINTER(_i),
-                                                    C.POINTER(C.c_float)]
-            L.mdc_device_free.argtypes = [_vp, _vp]
-            L.mdc_device_free.restype = None
-        if hasattr(L, "mdc_alloc_placed_device"):  # (absent from libraries built before round 6)
-            L.mdc_alloc_placed_device.argtypes = [_vp, _sz, _sz, _i64, C.c_uint, _i, _vp, C.POINTER(PlacedBuffers)]
-            L.mdc_free_placed_device.argtypes = [_vp, C.POINTER(PlacedBuffers)]
-            L.mdc_alloc_striped_set_device.argtypes = [_vp, _i, C.POINTER(_sz), _vp, C.POINTER(StripedSet)]
-            L.mdc_free_striped_set_device.argtypes = [_vp, C.POINTER(StripedSet)]
-            L.mdc_copy_to_host.argtypes = [_vp, _vp, _vp, _sz]
-        L.mdc_unmap_batch_device.argtypes = [_vp, _vp, _vp, _i64, C.c_uint, _vp]
-        L.mdc_process_batch_device.argtypes = [_vp, _vp, _vp, _i64, C.c_uint, _vp]
-        L.mdc_undistort_batch_device_f32.argtypes = [_vp, _vp, _vp, _i64, _vp]
-        L.mdc_pyramid_batch_device.argtypes = [_vp, _vp, _i, _i, _i, C.POINTER(_vp), _i64, _vp]
-        L.mdc_process_pyramid_batch_device.argtypes = [_vp, _vp, _vp, _i, C.POINTER(_vp), _i64, C.c_uint, _vp]
-        L.mdc_distort_points_device.argtypes = [_vp, C.POINTER(FovModel), _vp, _vp, _i64, _vp]
-        L.mdc_distort_points_host.argtypes = [_vp, C.POINTER(FovModel), _vp, _vp, _i64]
-        L.mdc_export_tables.argtypes = [_vp, _vp, _sz, C.POINTER(_sz)]
-        L.mdc_import_tables.argtypes = [_vp, _vp, _sz]
-        L.mdc_synchronize.argtypes = [_vp]
-        if hasattr(L, "mdc_device_pci_bus_id"):
-            L.mdc_device_pci_bus_id.argtypes = [_vp, C.c_char_p, _sz]
-        old_build = LIB_HIP_PATH != os.path.join(_PKG, "libmdc_hip.so")  # tools/sweep.py --libs: A/B against earlier builds
-        if not old_build or hasattr(L, "mdc_describe_launch"):
-            L.mdc_describe_launch.argtypes = [_vp, C.c_uint, _i, C.c_char_p, _sz]
-            L.mdc_vcal_plane_step_device.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]
-            L.mdc_tune_device.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_uint, _vp, C.POINTER(TuneResult)]
-            L.mdc_gradients_batch_device.argtypes = [_vp, _vp, _i, _i, _vp, _vp, C.c_int64, _vp]
-            if hasattr(L, "mdc_process_pyramid_gradients_batch_device"):
-                L.mdc_process_pyramid_gradients_batch_device.argtypes = [_vp, _vp, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i64,
-                                                                         C.c_uint, _i, _vp]
-            L.mdc_vcal_vignette_step_device.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]
-        if not old_build or hasattr(L, "mdc_vcal_index_create"):
-            L.mdc_vcal_index_create.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_vp)]
-            L.mdc_vcal_index_destroy.argtypes = [_vp]
-            L.mdc_vcal_index_destroy.restype = None
-            L.mdc_vcal_index_bytes.argtypes = [_vp]
-            L.mdc_vcal_index_bytes.restype = C.c_int64
-            L.mdc_vcal_index_entries.argtypes = [_vp]
-            L.mdc_vcal_index_entries.restype = C.c_int64
-            L.mdc_vcal_vignette_step_indexed_device.argtypes = [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]
-        if not old_build or hasattr(L, "mdc_vcal_solve_device"):
-            L.mdc_vcal_solve_device.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]
-            L.mdc_vcal_smooth_device.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp]
-            L.mdc_vcal_mask_coords_device.argtypes = [_vp, _vp, _vp, C.c_int64, _i, _i, _vp]
-            L.mdc_vcal_gradient_mask_device.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
-            L.mdc_vcal_scale_images_device.argtypes = [_vp, _vp, _i, C.c_int64, C.c_float, _vp, _vp]
-        if not old_build or hasattr(L, "mdc_vcal_plane_coords_device"):
-            L.mdc_vcal_plane_coords_device.argtypes = [_vp, C.POINTER(FovModel), _vp, _vp, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]
-        if not old_build or hasattr(L, "mdc_rcal_solve_device"):
-            L.mdc_rcal_leak_pad_device.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
-            L.mdc_rcal_init_e_device.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
-            L.mdc_rcal_rmse_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]
-            L.mdc_rcal_g_step_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]
-            L.mdc_rcal_index_create.argtypes = [_vp, _vp, _i, _i, _i, _vp, C.POINTER(_vp)]
-            L.mdc_rcal_index_destroy.argtypes = [_vp]
-            L.mdc_rcal_index_destroy.restype = None
-            for n in ("mdc_rcal_index_bytes", "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain"):
-                getattr(L, n).argtypes = [_vp]
-                getattr(L, n).restype = C.c_int64
-            L.mdc_rcal_g_step_indexed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
-            L.mdc_rcal_e_step_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]
-            L.mdc_rcal_rescale_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
-            L.mdc_rcal_solve_device.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, C.c_uint, _vp, _vp, C.POINTER(RcalLog), _vp]
-            L.mdc_copy_to_device.argtypes = [_vp, _vp, _vp, _sz]
-        for n in HIP_SYMBOLS:
-            if old_build and not hasattr(L, n):
-                continue
-            if n not in ("mdc_destroy", "mdc_last_error", "mdc_build_flags", "mdc_code_id", "mdc_device_free", "mdc_host_alloc", "mdc_host_free", "mdc_vcal_index_destroy",
-                         "mdc_vcal_index_bytes", "mdc_vcal_index_entries", "mdc_rcal_index_destroy", "mdc_rcal_index_bytes",
-                         "mdc_rcal_index_entries", "mdc_rcal_index_longest_chain"):
-                getattr(L, n).restype = _i
-        _hip = L
+        # LIB_HIP_PATH is read here, not at import: tools/sweep.py and the tests bind module copies to other builds by reassigning it
+        _hip = _load(LIB_HIP_PATH, HIP_API, product=LIB_HIP_PATH == os.path.join(_PKG, "libmdc_hip.so"))
     return _hip
 
 
@@ -317,100 +348,17 @@ def host_lib():
     global _host
     if _host is None:
         hip_lib()
-        if not os.path.exists(LIB_HOST_PATH):
-            raise OSError("%s not built: run `python -m mono_dataset_code_amd.build`" % LIB_HOST_PATH)
-        L = C.CDLL(LIB_HOST_PATH)
-        L.mdch_fov_create.argtypes = [C.c_char_p]
-        L.mdch_fov_create.restype = _vp
-        L.mdch_fov_destroy.argtypes = [_vp]
-        L.mdch_fov_destroy.restype = None
-        for n in ("mdch_fov_valid", "mdch_fov_has_gpu"):
-            getattr(L, n).argtypes = [_vp]
-            getattr(L, n).restype = _i
-        L.mdch_fov_dims.argtypes = [_vp, _vp]
-        L.mdch_fov_dims.restype = None
-        L.mdch_fov_intrinsics.argtypes = [_vp, _vp]
-        L.mdch_fov_intrinsics.restype = None
-        L.mdch_fov_model.argtypes = [_vp, C.POINTER(FovModel)]
-        L.mdch_fov_model.restype = None
-        L.mdch_fov_remap.argtypes = [_vp, _vp, _vp]
-        L.mdch_fov_remap.restype = _i
-        L.mdch_fov_distort.argtypes = [_vp, _vp, _vp, _i]
-        L.mdch_fov_distort.restype = None
-        L.mdch_fov_undistort_f32.argtypes = [_vp, _vp, _vp, _i, _i]
-        L.mdch_fov_undistort_f32.restype = None
-        L.mdch_fov_undistort_u8.argtypes = [_vp, _vp, _vp, _i, _i]
-        L.mdch_fov_undistort_u8.restype = None
-        L.mdch_photo_create.argtypes = [C.c_char_p, C.c_char_p, _i, _i]
-        L.mdch_photo_create.restype = _vp
-        L.mdch_photo_destroy.argtypes = [_vp]
-        L.mdch_photo_destroy.restype = None
-        for n in ("mdch_photo_valid", "mdch_photo_has_gpu"):
-            getattr(L, n).argtypes = [_vp]
-            getattr(L, n).restype = _i
-        L.mdch_photo_ginv.argtypes = [_vp, _vp]
-        L.mdch_photo_ginv.restype = _i
-        L.mdch_photo_g.argtypes = [_vp, _vp]
-        L.mdch_photo_g.restype = _i
-        L.mdch_photo_vignette.argtypes = [_vp, _vp, _vp]
-        L.mdch_photo_vignette.restype = _i
-        L.mdch_photo_unmap.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i]
-        L.mdch_photo_unmap.restype = None
-        L.mdch_bind.argtypes = [_vp, _vp, _vp]
-        L.mdch_bind.restype = _i
-        L.mdch_pack_tables.argtypes = [_vp, _vp, _vp, _sz, C.POINTER(_sz)]
-        L.mdch_pack_tables.restype = _i
-        L.mdch_reader_create.argtypes = [C.c_char_p]
-        L.mdch_reader_create.restype = _vp
-        L.mdch_reader_destroy.argtypes = [_vp]
-        L.mdch_reader_destroy.restype = None
-        L.mdch_reader_num_images.argtypes = [_vp]
-        L.mdch_reader_timestamp.argtypes = [_vp, _i]
-        L.mdch_reader_timestamp.restype = C.c_double
-        L.mdch_reader_exposure.argtypes = [_vp, _i]
-        L.mdch_reader_exposure.restype = C.c_float
-        L.mdch_reader_dims.argtypes = [_vp, _vp]
-        L.mdch_reader_dims.restype = None
-        L.mdch_reader_get_image.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, C.POINTER(C.c_double), C.POINTER(C.c_float)]
-        L.mdch_reader_get_images.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_long, _vp]
-        L.mdch_reader_get_images_device.argtypes = [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(DeviceOutputs), _vp]
-        L.mdch_reader_context.argtypes = [_vp]
-        L.mdch_reader_context.restype = _vp
-        L.mdch_reader_device.argtypes = [_vp]
-        L.mdch_reader_get_raw.argtypes = [_vp, _i, _vp, C.c_long, _vp]
-        if hasattr(L, "mdch_reader_get_images_raw_device"):
-            L.mdch_reader_get_images_raw_device.argtypes = [_vp, _i, _i, _i, _vp, _vp]
-            L.mdch_reader_raw_dims.argtypes = [_vp, _vp]
-            L.mdch_reader_raw_dims.restype = None
-        L.mdch_reader_set_threads.argtypes = [_vp, _i]
-        L.mdch_reader_set_threads.restype = None
-        L.mdch_reader_set_prefetch.argtypes = [_vp, _i]
-        L.mdch_reader_set_gpu_jpeg.argtypes = [_vp, _i]
-        L.mdch_reader_set_lookahead.argtypes = [_vp, _i]
-        L.mdch_reader_set_prefetch.restype = None
-        L.mdch_reader_last_error.argtypes = [_vp]
-        L.mdch_reader_last_error.restype = C.c_char_p
-        L.mdch_reader_prefetch_stats.argtypes = [_vp, _vp]
-        L.mdch_reader_prefetch_stats.restype = None
-        L.mdch_reader_device_stats.argtypes = [_vp, _i, _vp, _vp]
-        L.mdch_decode_gray8.argtypes = [_vp, _sz, _vp, _sz, _vp, C.c_char_p, _sz]
-        L.mdch_jpeg_record_bytes.argtypes = [_i, _i, _vp]
-        L.mdch_jpeg_record_bytes.restype = _sz
-        L.mdch_decode_jpeg_record.argtypes = [_vp, _sz, _vp, _sz, _i, _vp, C.c_char_p, _sz]
-        L.mdch_jpeg_stream.argtypes = [_vp, _sz, _vp, _sz, _vp, C.c_char_p, _sz]
-        L.mdch_jpeg_stream.restype = C.c_longlong
-        L.mdch_image_alloc.argtypes = [C.c_ulong]
-        L.mdch_image_alloc.restype = _vp
-        L.mdch_image_free.argtypes = [_vp]
-        L.mdch_image_free.restype = None
-        L.mdch_image_pool_trim.restype = None
-        L.mdch_image_pool_idle_bytes.restype = C.c_ulong
-        _host = L
+        _host = _load(LIB_HOST_PATH, HOST_API)
     return _host
 
 
 def _np_ptr(a):
     return a.ctypes.data_as(_vp) if a is not None else None
+
+
+def _stream(stream):
+    """a hipStream_t given as an integer -> the void* argument (0: the null stream)"""
+    return stream if stream else None
 
 
 def _f32(a):
@@ -559,30 +507,29 @@ class Context:
 
     def jpeg_huffman_batch(self, d_streams, stream_stride, d_records, record_bytes, w, h, blocks_w, blocks_rows, nframes, d_status, stream=0):
         self._chk(self._L.mdc_jpeg_huffman_batch_device(self._h, d_streams, stream_stride, d_records, record_bytes, w, h, blocks_w, blocks_rows,
-                                                        nframes, d_status, stream if stream else None))
+                                                        nframes, d_status, _stream(stream)))
 
     def jpeg_idct_batch(self, d_records, record_bytes, d_frames, w, h, blocks_w, blocks_rows, nframes, stream=0):
         self._chk(self._L.mdc_jpeg_idct_batch_device(self._h, d_records, record_bytes, d_frames, w, h, blocks_w, blocks_rows, nframes,
-                                                     stream if stream else None))
+                                                     _stream(stream)))
 
     # device-pointer batched calls (addresses as ints)
     def unmap_batch(self, d_in, d_out, nframes, flags, stream=0):
-        self._chk(self._L.mdc_unmap_batch_device(self._h, d_in, d_out, nframes, flags, stream if stream else None))
+        self._chk(self._L.mdc_unmap_batch_device(self._h, d_in, d_out, nframes, flags, _stream(stream)))
 
     def process_batch(self, d_in, d_out, nframes, flags, stream=0):
-        self._chk(self._L.mdc_process_batch_device(self._h, d_in, d_out, nframes, flags, stream if stream else None))
+        self._chk(self._L.mdc_process_batch_device(self._h, d_in, d_out, nframes, flags, _stream(stream)))
 
     def undistort_batch_f32(self, d_in, d_out, nframes, stream=0):
-        self._chk(self._L.mdc_undistort_batch_device_f32(self._h, d_in, d_out, nframes, stream if stream else None))
+        self._chk(self._L.mdc_undistort_batch_device_f32(self._h, d_in, d_out, nframes, _stream(stream)))
 
     def pyramid_batch(self, d_base, w, h, levels, d_levels, nframes, stream=0):
         arr = (_vp * max(1, len(d_levels)))(*d_levels)
-        self._chk(self._L.mdc_pyramid_batch_device(self._h, d_base, w, h, levels, arr, nframes, stream if stream else None))
+        self._chk(self._L.mdc_pyramid_batch_device(self._h, d_base, w, h, levels, arr, nframes, _stream(stream)))
 
     def process_pyramid_batch(self, d_in, d_base, levels, d_levels, nframes, flags, stream=0):
         arr = (_vp * max(1, len(d_levels)))(*d_levels)
-        self._chk(self._L.mdc_process_pyramid_batch_device(self._h, d_in, d_base, levels, arr, nframes, flags,
-                                                           stream if stream else None))
+        self._chk(self._L.mdc_process_pyramid_batch_device(self._h, d_in, d_base, levels, arr, nframes, flags, _stream(stream)))
 
     def process_pyramid_gradients_batch(self, d_in, d_base, levels, d_levels, d_dI, d_abs, nframes, flags, chunk_frames=0, stream=0):
         """base + levels + (I, dx, dy) / absSquaredGrad of every level in one call; d_dI / d_abs: one address per level (0 = base)."""
@@ -590,18 +537,18 @@ class Context:
         di = (_vp * levels)(*d_dI)
         ab = (_vp * levels)(*d_abs)
         self._chk(self._L.mdc_process_pyramid_gradients_batch_device(self._h, d_in, d_base, levels, lv, di, ab, nframes, flags, chunk_frames,
-                                                                     stream if stream else None))
+                                                                     _stream(stream)))
 
     def distort_points_host(self, model, x, y):
         assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size
         self._chk(self._L.mdc_distort_points_host(self._h, C.byref(model), _np_ptr(x), _np_ptr(y), x.size))
 
     def distort_points_device(self, model, d_x, d_y, n, stream=0):
-        self._chk(self._L.mdc_distort_points_device(self._h, C.byref(model), d_x, d_y, n, stream if stream else None))
+        self._chk(self._L.mdc_distort_points_device(self._h, C.byref(model), d_x, d_y, n, _stream(stream)))
 
     def synth_frames(self, d_out, first_frame, nframes, npix, seed, stream=0):
         """(bench / test utility, libmdc_bench.so -- not part of the product ABI)"""
-        rc = bench_lib().mdcb_synth_frames_device(self.device(), d_out, first_frame, nframes, npix, seed, stream if stream else None)
+        rc = bench_lib().mdcb_synth_frames_device(self.device(), d_out, first_frame, nframes, npix, seed, _stream(stream))
         if rc != 0:
             raise MdcError(rc, "mdcb_synth_frames_device failed")
 
@@ -626,14 +573,14 @@ class Context:
         a, b = (_vp * max(ni, 1))(*d_ins), (_vp * max(no, 1))(*d_outs)
         bi, bo = _i(0), _i(0)
         ms = (C.c_float * max(ni * no, 1))()
-        self._chk(self._L.mdc_tune_placement_device(self._h, a, ni, b, no, nframes, flags, stream if stream else None, C.byref(bi), C.byref(bo), ms))
+        self._chk(self._L.mdc_tune_placement_device(self._h, a, ni, b, no, nframes, flags, _stream(stream), C.byref(bi), C.byref(bo), ms))
         return bi.value, bo.value, [[float(ms[i * no + j]) for j in range(no)] for i in range(ni)]
 
     def alloc_placed(self, nframes, flags, strategy=PLACE_AUTO, stream=0, in_bytes=0, out_bytes=0):
         """A frame buffer and a result buffer for nframes frames of the pass `flags`, placed by measurement (include/mdc_hip.h:
         mdc_alloc_placed_device).  -> PlacedBuffers; give it back with free_placed()."""
         b = PlacedBuffers()
-        self._chk(self._L.mdc_alloc_placed_device(self._h, in_bytes, out_bytes, nframes, flags, strategy, stream if stream else None, C.byref(b)))
+        self._chk(self._L.mdc_alloc_placed_device(self._h, in_bytes, out_bytes, nframes, flags, strategy, _stream(stream), C.byref(b)))
         return b
 
     def free_placed(self, b):
@@ -644,7 +591,7 @@ class Context:
         -> StripedSet (d_ptr[k] = buffer k); give it back with free_striped_set()."""
         b = StripedSet()
         arr = (_sz * len(sizes))(*[int(x) for x in sizes])
-        self._chk(self._L.mdc_alloc_striped_set_device(self._h, len(sizes), arr, stream if stream else None, C.byref(b)))
+        self._chk(self._L.mdc_alloc_striped_set_device(self._h, len(sizes), arr, _stream(stream), C.byref(b)))
         return b
 
     def free_striped_set(self, b):
@@ -676,22 +623,22 @@ class Context:
 
     def marker(self, ident, stream=0):
         """(bench utility, libmdc_bench.so) a no-op kernel named mdcb_marker_kernel on `stream`: a cut mark in a profiler's kernel trace"""
-        if bench_lib().mdcb_marker_device(self.device(), ident, stream if stream else None) != 0:
+        if bench_lib().mdcb_marker_device(self.device(), ident, _stream(stream)) != 0:
             raise MdcError(-4, "mdcb_marker_device failed")
 
     def ceiling_mix(self, d_read, read_bytes, d_write, write_bytes, blocks=16384, span=0, stream=0):
         """(bench utility, libmdc_bench.so -- not part of the product ABI)"""
-        rc = bench_lib().mdcb_ceiling_mix_device(self.device(), d_read, read_bytes, d_write, write_bytes, blocks, span, stream if stream else None)
+        rc = bench_lib().mdcb_ceiling_mix_device(self.device(), d_read, read_bytes, d_write, write_bytes, blocks, span, _stream(stream))
         if rc != 0:
             raise MdcError(rc, "mdcb_ceiling_mix_device failed")
 
     def tune(self, d_in, d_out, nframes, flags, stream=0):
         r = TuneResult()
-        self._chk(self._L.mdc_tune_device(self._h, d_in, d_out, nframes, flags, stream if stream else None, C.byref(r)))
+        self._chk(self._L.mdc_tune_device(self._h, d_in, d_out, nframes, flags, _stream(stream), C.byref(r)))
         return r
 
     def gradients_batch(self, d_level, w, h, d_dI, d_abs, nframes, stream=0):
-        self._chk(self._L.mdc_gradients_batch_device(self._h, d_level, w, h, d_dI, d_abs, nframes, stream if stream else None))
+        self._chk(self._L.mdc_gradients_batch_device(self._h, d_level, w, h, d_dI, d_abs, nframes, _stream(stream)))
 
     def vcal_plane_step(self, d_images, d_p2x, d_p2y, d_plane_color, d_vig, oth2, stream=0):
         """torch tensors on the device; d_plane_color is updated in place -> (FF, FC, E, R)."""
@@ -704,7 +651,7 @@ class Context:
         er = torch.zeros(2, dtype=torch.float64, device=d_images.device)
         self._chk(self._L.mdc_vcal_plane_step_device(self._h, d_images.data_ptr(), d_p2x.data_ptr(), d_p2y.data_ptr(), n, w, h, npnt,
                                                      d_plane_color.data_ptr(), d_vig.data_ptr(), int(oth2), ff.data_ptr(), fc.data_ptr(),
-                                                     er.data_ptr(), stream if stream else None))
+                                                     er.data_ptr(), _stream(stream)))
         e, r = er.cpu().tolist()
         return ff, fc, e, r
 
@@ -719,7 +666,7 @@ class Context:
         er = torch.zeros(2, dtype=torch.float64, device=d_images.device)
         self._chk(self._L.mdc_vcal_vignette_step_device(self._h, d_images.data_ptr(), d_p2x.data_ptr(), d_p2y.data_ptr(), n, w, h, npnt,
                                                         d_plane_color.data_ptr(), d_vig.data_ptr(), int(oth2), tt.data_ptr(), ct.data_ptr(),
-                                                        er.data_ptr(), stream if stream else None))
+                                                        er.data_ptr(), _stream(stream)))
         e, r = er.cpu().tolist()
         return tt, ct, e, r
 
@@ -730,23 +677,23 @@ class Context:
         er = np.zeros((max(max_iterations, 0), 4), np.float64)
         self._chk(self._L.mdc_vcal_solve_device(self._h, d_images.data_ptr(), d_p2x.data_ptr(), d_p2y.data_ptr(), n, w, h, d_p2x.shape[1],
                                                 d_plane_color.data_ptr(), d_vig.data_ptr(), int(max_iterations), int(outlier_th),
-                                                _np_ptr(er), stream if stream else None))
+                                                _np_ptr(er), _stream(stream)))
         return er
 
     def vcal_scale_images(self, d_images, mean_exposure, d_exposure_times, stream=0):
         """image k = mean_exposure * image k / exposure_time k, in place (src/main_vignetteCalib.cpp:286-291)."""
         n = d_images.shape[0]
         self._chk(self._L.mdc_vcal_scale_images_device(self._h, d_images.data_ptr(), n, d_images[0].numel(), float(mean_exposure),
-                                                       d_exposure_times.data_ptr(), stream if stream else None))
+                                                       d_exposure_times.data_ptr(), _stream(stream)))
 
     def vcal_gradient_mask(self, d_images, max_abs_grad=255, stream=0):
         """Gradient mask of a stack of calibration images (n, h, w), in place (src/main_vignetteCalib.cpp:293-301)."""
         n, h, w = d_images.shape
-        self._chk(self._L.mdc_vcal_gradient_mask_device(self._h, d_images.data_ptr(), n, w, h, int(max_abs_grad), stream if stream else None))
+        self._chk(self._L.mdc_vcal_gradient_mask_device(self._h, d_images.data_ptr(), n, w, h, int(max_abs_grad), _stream(stream)))
 
     def vcal_mask_coords(self, d_x, d_y, w, h, stream=0):
         """NaN coordinates for plane points outside the w x h image (src/main_vignetteCalib.cpp:345-357), in place."""
-        self._chk(self._L.mdc_vcal_mask_coords_device(self._h, d_x.data_ptr(), d_y.data_ptr(), d_x.numel(), w, h, stream if stream else None))
+        self._chk(self._L.mdc_vcal_mask_coords_device(self._h, d_x.data_ptr(), d_y.data_ptr(), d_x.numel(), w, h, _stream(stream)))
 
     def vcal_plane_coords(self, model, gw, gh, facw=5.0, fach=5.0, corners=None, hk=None, stream=0):
         """Plane -> image coordinates of n frames (src/main_vignetteCalib.cpp:230-258, :284, :345-357) -> (p2x, p2y, hk): device
@@ -766,7 +713,7 @@ class Context:
         p2y = torch.empty_like(p2x)
         self._chk(self._L.mdc_vcal_plane_coords_device(self._h, C.byref(model) if model is not None else None,
                                                        corners.data_ptr() if corners is not None else None, hk.data_ptr(), n, gw, gh,
-                                                       float(facw), float(fach), p2x.data_ptr(), p2y.data_ptr(), stream if stream else None))
+                                                       float(facw), float(fach), p2x.data_ptr(), p2y.data_ptr(), _stream(stream)))
         return p2x, p2y, hk
 
     def vcal_smooth(self, d_vig, w, h, stream=0):
@@ -774,7 +721,7 @@ class Context:
         import torch
 
         tt, ct = torch.empty_like(d_vig), torch.empty_like(d_vig)
-        self._chk(self._L.mdc_vcal_smooth_device(self._h, d_vig.data_ptr(), w, h, tt.data_ptr(), ct.data_ptr(), stream if stream else None))
+        self._chk(self._L.mdc_vcal_smooth_device(self._h, d_vig.data_ptr(), w, h, tt.data_ptr(), ct.data_ptr(), _stream(stream)))
         return tt, ct
 
     def vcal_index(self, d_images, d_p2x, d_p2y, stream=0):
@@ -790,7 +737,7 @@ class Context:
         ct = torch.empty_like(tt)
         er = torch.zeros(2, dtype=torch.float64, device=d_vig.device)
         self._chk(self._L.mdc_vcal_vignette_step_indexed_device(self._h, index._h, d_plane_color.data_ptr(), d_vig.data_ptr(), int(oth2),
-                                                                tt.data_ptr(), ct.data_ptr(), er.data_ptr(), stream if stream else None))
+                                                                tt.data_ptr(), ct.data_ptr(), er.data_ptr(), _stream(stream)))
         e, r = er.cpu().tolist()
         return tt, ct, e, r
 
@@ -799,7 +746,7 @@ class Context:
     def rcal_leak_pad(self, d_images, leak_padding=2, stream=0):
         """Leak padding (src/main_responseCalib.cpp:208-233), in place."""
         n, h, w = d_images.shape
-        self._chk(self._L.mdc_rcal_leak_pad_device(self._h, d_images.data_ptr(), n, w, h, int(leak_padding), stream if stream else None))
+        self._chk(self._L.mdc_rcal_leak_pad_device(self._h, d_images.data_ptr(), n, w, h, int(leak_padding), _stream(stream)))
 
     def rcal_init_e(self, d_images, stream=0):
         """Initial irradiance (:250-258) -> E (h*w float64)."""
@@ -807,7 +754,7 @@ class Context:
 
         n, h, w = d_images.shape
         E = torch.empty(h * w, dtype=torch.float64, device=d_images.device)
-        self._chk(self._L.mdc_rcal_init_e_device(self._h, d_images.data_ptr(), n, w, h, E.data_ptr(), stream if stream else None))
+        self._chk(self._L.mdc_rcal_init_e_device(self._h, d_images.data_ptr(), n, w, h, E.data_ptr(), _stream(stream)))
         return E
 
     def _rcal_pair(self, d):
@@ -820,7 +767,7 @@ class Context:
         n, h, w = d_images.shape
         out = self._rcal_pair(d_images)
         self._chk(self._L.mdc_rcal_rmse_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_G.data_ptr(), d_E.data_ptr(),
-                                               out.data_ptr(), stream if stream else None))
+                                               out.data_ptr(), _stream(stream)))
         a, b = out.cpu().tolist()
         return a, b
 
@@ -828,7 +775,7 @@ class Context:
         """G step (:285-304), direct (fixed-point) mode; d_G is overwritten."""
         n, h, w = d_images.shape
         self._chk(self._L.mdc_rcal_g_step_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_E.data_ptr(), d_G.data_ptr(),
-                                                 stream if stream else None))
+                                                 _stream(stream)))
 
     def rcal_index(self, d_images, stream=0):
         """Exact-order index of the stack (mdc_rcal_index_create)."""
@@ -836,15 +783,14 @@ class Context:
 
     def rcal_g_step_indexed(self, index, d_exposure, d_E, d_G, stream=0):
         """G step in the reference's order (bit-identical); d_G is overwritten."""
-        self._chk(self._L.mdc_rcal_g_step_indexed_device(self._h, index._h, d_exposure.data_ptr(), d_E.data_ptr(), d_G.data_ptr(),
-                                                         stream if stream else None))
+        self._chk(self._L.mdc_rcal_g_step_indexed_device(self._h, index._h, d_exposure.data_ptr(), d_E.data_ptr(), d_G.data_ptr(), _stream(stream)))
 
     def rcal_e_step(self, d_images, d_exposure, d_G, d_E, stream=0):
         """E step (:319-339), d_E in place -> (rmse, num) of G with the E before the step."""
         n, h, w = d_images.shape
         out = self._rcal_pair(d_images)
         self._chk(self._L.mdc_rcal_e_step_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_G.data_ptr(), d_E.data_ptr(),
-                                                 out.data_ptr(), stream if stream else None))
+                                                 out.data_ptr(), _stream(stream)))
         a, b = out.cpu().tolist()
         return a, b
 
@@ -853,7 +799,7 @@ class Context:
         n, h, w = d_images.shape
         a, b = self._rcal_pair(d_images), self._rcal_pair(d_images)
         self._chk(self._L.mdc_rcal_rescale_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, d_G.data_ptr(), d_E.data_ptr(),
-                                                  a.data_ptr(), b.data_ptr(), stream if stream else None))
+                                                  a.data_ptr(), b.data_ptr(), _stream(stream)))
         return tuple(a.cpu().tolist()), tuple(b.cpu().tolist())
 
     def rcal_solve(self, d_images, d_exposure, iterations=10, mode=RCAL_EXACT_ORDER, stream=0):
@@ -867,7 +813,7 @@ class Context:
         its = (RcalIter * max(int(iterations), 1))()
         lg = RcalLog(0.0, 0.0, C.cast(its, C.POINTER(RcalIter)))
         self._chk(self._L.mdc_rcal_solve_device(self._h, d_images.data_ptr(), d_exposure.data_ptr(), n, w, h, int(iterations), int(mode),
-                                                G.data_ptr(), E.data_ptr(), C.byref(lg), stream if stream else None))
+                                                G.data_ptr(), E.data_ptr(), C.byref(lg), _stream(stream)))
         names = [f[0] for f in RcalIter._fields_]
         log = {"init_rmse": lg.init_rmse, "init_num": lg.init_num,
                "iters": [{k: getattr(its[i], k) for k in names} for i in range(int(iterations))]}
@@ -886,7 +832,7 @@ class VcalIndex:
         self._h = _vp()
         n, self.h, self.w = d_images.shape
         ctx._chk(self._L.mdc_vcal_index_create(ctx._h, d_images.data_ptr(), d_p2x.data_ptr(), d_p2y.data_ptr(), n, self.w, self.h,
-                                               d_p2x.shape[1], stream if stream else None, C.byref(self._h)))
+                                               d_p2x.shape[1], _stream(stream), C.byref(self._h)))
         self.bytes = self._L.mdc_vcal_index_bytes(self._h)
         self.entries = self._L.mdc_vcal_index_entries(self._h)
 
@@ -909,7 +855,7 @@ class RcalIndex:
         self._L = ctx._L
         self._h = _vp()
         n, self.h, self.w = d_images.shape
-        ctx._chk(self._L.mdc_rcal_index_create(ctx._h, d_images.data_ptr(), n, self.w, self.h, stream if stream else None, C.byref(self._h)))
+        ctx._chk(self._L.mdc_rcal_index_create(ctx._h, d_images.data_ptr(), n, self.w, self.h, _stream(stream), C.byref(self._h)))
         self.bytes = self._L.mdc_rcal_index_bytes(self._h)
         self.entries = self._L.mdc_rcal_index_entries(self._h)
         self.longest_chain = self._L.mdc_rcal_index_longest_chain(self._h)

@@ -233,3 +233,140 @@ def test_every_environment_variable_is_documented():
     assert len(used) >= 15, used
     missing = sorted(v for v in used if ("`%s" % v) not in table)
     assert not missing, "undocumented environment variables: %s" % missing
+
+
+C_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t,
+             "long": ctypes.c_long, "unsigned long": ctypes.c_ulong, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+             "double": ctypes.c_double}
+
+
+def prototypes(header, prefix):
+    """name -> (return type, [parameter, ...]) as C text, of every `MDC_API <ret> name(params);` the header declares (comments
+    stripped; a declaration may span lines)."""
+    txt = open(os.path.join(ROOT, "include", header)).read()
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", "", txt, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"\bMDC_API\s+([\w\s*]+?)\s*\b(%s\w+)\s*\(([^()]*)\)\s*;" % prefix, txt):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        assert name not in out, name
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return out
+
+
+def is_pointer_type(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def scalar_type(text):
+    """the ctypes type of a scalar parameter or return type given as C text (`const`, and a parameter's name, dropped)"""
+    words = [w for w in text.split() if w != "const"]
+    if " ".join(words) not in C_SCALARS:
+        words = words[:-1]  # the parameter's name
+    return C_SCALARS[" ".join(words)]
+
+
+def signature_mismatches(table, protos):
+    bad = []
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        if ret == "void":
+            ok = restype is None
+        elif ret == "const char*":
+            ok = restype is ctypes.c_char_p
+        elif "*" in ret:
+            ok = restype is ctypes.c_void_p
+        else:
+            ok = restype is scalar_type(ret)
+        if not ok:
+            bad.append("%s: returns %s, declared %r" % (name, ret, restype))
+        if len(argtypes) != len(params):
+            bad.append("%s: %d parameters, %d declared" % (name, len(params), len(argtypes)))
+            continue
+        for k, (p, t) in enumerate(zip(params, argtypes)):
+            if not (is_pointer_type(t) if ("*" in p or "[" in p) else t is scalar_type(p)):
+                bad.append("%s: parameter %d is %s, declared %r" % (name, k, p, t))
+    return bad
+
+
+def header_prototypes():
+    host = prototypes("mdc_host.h", "mdch_")
+    for name, proto in prototypes(os.path.join("mono_dataset_code", "ExposureImage.h"), "mdch_").items():  # the two image-pool functions
+        assert host.setdefault(name, proto) == proto, name
+    return {"HIP_API": prototypes("mdc_hip.h", "mdc_"), "HOST_API": host, "BENCH_API": prototypes("mdc_bench.h", "mdcb_")}
+
+
+def test_signature_tables_match_the_headers():
+    """capi's tables, the only place the Python side declares a signature, against every MDC_API declaration: the same
+    functions, and for each the return type, the number of parameters, and per parameter a ctypes pointer type for a C pointer
+    or array and THE ctypes type of the C type for a scalar."""
+    from mono_dataset_code_amd import capi
+
+    for table_name, protos in header_prototypes().items():
+        table = getattr(capi, table_name)
+        assert len(protos) >= 6 and sorted(table) == sorted(protos), table_name
+        assert signature_mismatches(table, protos) == [], table_name
+    assert (capi.HIP_SYMBOLS, capi.HOST_SYMBOLS, capi.BENCH_SYMBOLS) == (list(capi.HIP_API), list(capi.HOST_API), list(capi.BENCH_API))
+    # the check can fail: a wrong scalar, a scalar for a pointer, a missing parameter, a wrong return type
+    protos = header_prototypes()["HIP_API"]
+    for name, wrong in (("mdc_set_option", (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64])),
+                        ("mdc_copy_to_host", (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t])),
+                        ("mdc_synchronize", (ctypes.c_int, [])),
+                        ("mdc_vcal_index_bytes", (ctypes.c_int, [ctypes.c_void_p])),
+                        ("mdc_host_free", (ctypes.c_int, [ctypes.c_void_p]))):
+        assert len(signature_mismatches(dict(capi.HIP_API, **{name: wrong}), protos)) == 1, name
+
+
+def test_capi_calls_only_declared_functions():
+    """Every mdc_* / mdch_* / mdcb_* function capi.py calls, or takes from a library object, is a row of one of the tables."""
+    from mono_dataset_code_amd import capi
+
+    src = open(os.path.join(ROOT, "mono_dataset_code_amd", "capi.py")).read()
+    used = set(re.findall(r"\b(mdc[hb]?_\w+)\(", src)) | set(re.findall(r"\.\s*(mdc[hb]?_\w+)\b", src))
+    assert len(used) >= 100, len(used)
+    assert sorted(used - set(capi.HIP_API) - set(capi.HOST_API) - set(capi.BENCH_API)) == []
+
+
+def test_loader_binds_the_table_and_nothing_else():
+    """capi._bind: the in-tree library must have every row (the error names the missing symbol and says to rebuild); another
+    build may lack some, which are then not reachable; neither is anything the table does not declare."""
+    from types import SimpleNamespace
+
+    from mono_dataset_code_amd import capi
+
+    table = {"mdc_a": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int]), "mdc_gone": (ctypes.c_char_p, []), "mdc_b": (None, [])}
+
+    def stand_in():
+        return SimpleNamespace(mdc_a=SimpleNamespace(), mdc_b=SimpleNamespace(), mdc_undeclared=SimpleNamespace())
+
+    with pytest.raises(OSError) as e:
+        capi._bind(stand_in(), table, True)
+    assert "mdc_gone" in str(e.value) and "rebuild" in str(e.value)
+    lib = stand_in()
+    ns = capi._bind(lib, table, False)
+    assert sorted(vars(ns)) == ["mdc_a", "mdc_b"] and not hasattr(ns, "mdc_gone") and not hasattr(ns, "mdc_undeclared")
+    with pytest.raises(AttributeError, match="mdc_gone"):
+        ns.mdc_gone
+    for n in ("mdc_a", "mdc_b"):
+        assert getattr(ns, n) is getattr(lib, n) and (getattr(ns, n).restype, getattr(ns, n).argtypes) == table[n]
+    # the real libraries, all three in-tree: exactly their tables, each function marshalled as its row says
+    for L, table in ((capi.hip_lib(), capi.HIP_API), (capi.host_lib(), capi.HOST_API), (capi.bench_lib(), capi.BENCH_API)):
+        assert sorted(vars(L)) == sorted(table)
+        for n, (restype, argtypes) in table.items():
+            assert getattr(L, n).restype is restype and list(getattr(L, n).argtypes) == argtypes, n
+    assert not hasattr(capi.hip_lib(), "hipMalloc") and not hasattr(capi.host_lib(), "mdc_create")
+
+
+def test_signatures_are_declared_nowhere_else():
+    """No argtypes / restype assignment in capi.py outside the loader, and none for an mdch_* function in the reader tests."""
+    import inspect
+
+    from mono_dataset_code_amd import capi
+
+    assign = r"\.\s*(argtypes|restype)\b[^=\n]*=(?!=)"
+    src = open(os.path.join(ROOT, "mono_dataset_code_amd", "capi.py")).read()
+    loader = inspect.getsource(capi._bind)
+    assert src.count(loader) == 1 and re.search(assign, loader)
+    assert re.findall(assign, src.replace(loader, "")) == []
+    for f in ("test_reader.py", "test_reader_cpu.py"):
+        txt = open(os.path.join(ROOT, "tests", f)).read()
+        assert re.findall(r"mdch_\w+\s*\.\s*(?:argtypes|restype)\b[^=\n]*=(?!=)", txt) == [], f

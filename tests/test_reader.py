@@ -703,9 +703,6 @@ def test_image_pool_slabs():
     from mono_dataset_code_amd import capi
 
     L = capi.host_lib()
-    L.mdch_image_alloc.restype = ctypes.c_void_p
-    L.mdch_image_alloc.argtypes = [ctypes.c_ulong]
-    L.mdch_image_free.argtypes = [ctypes.c_void_p]
     L.mdch_image_pool_trim()
     base_idle = L.mdch_image_pool_idle_bytes()
     n = 640 * 480 + 4096  # (a size no other test's images have: a slab shared with a reader that is still open would break the adjacency below)

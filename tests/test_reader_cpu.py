@@ -371,10 +371,6 @@ import ctypes, os, sys
 sys.path.insert(0, %r)
 from mono_dataset_code_amd import capi
 L = capi.host_lib()
-L.mdch_image_alloc.restype = ctypes.c_void_p
-L.mdch_image_alloc.argtypes = [ctypes.c_ulong]
-L.mdch_image_free.argtypes = [ctypes.c_void_p]
-L.mdch_image_pool_idle_bytes.restype = ctypes.c_size_t
 a = L.mdch_image_alloc(640 * 480)
 b = L.mdch_image_alloc(640 * 480)
 assert a and b and a != b
