@@ -193,16 +193,25 @@ def build_host(force=False):
 BIN = os.path.join(PKG, "bin")
 RESPONSE_CALIB = os.path.join(BIN, "responseCalib")
 RESPONSE_CALIB_SOURCE = os.path.join(CSRC, "programs", "responseCalib.cpp")
+PLAY_DATASET = os.path.join(BIN, "playDataset")
+PLAY_DATASET_SOURCE = os.path.join(CSRC, "programs", "playDataset.cpp")
 
 
 def build_programs(force=False):
-    """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so."""
+    """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so;
+    bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so."""
     build_host(force)
+    build_jenc(force)
     os.makedirs(BIN, exist_ok=True)
     deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RESPONSE_CALIB, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
               RESPONSE_CALIB_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-Wl,-rpath,$ORIGIN/..", "-o", RESPONSE_CALIB])
+    deps = [PLAY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
+            os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
+    if force or _stale(PLAY_DATASET, deps):
+        _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
+              PLAY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-Wl,-rpath,$ORIGIN/..", "-o", PLAY_DATASET])
     return RESPONSE_CALIB
 
 
@@ -216,6 +225,20 @@ def build_bench(force=False):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-I" + INC, BENCH_SOURCE,
               "-Wl,--version-script=" + EXPORT_MAP, "-o", LIB_BENCH])
     return LIB_BENCH
+
+
+LIB_JENC = os.path.join(PKG, "libmdc_jenc.so")
+JENC_SOURCE = os.path.join(CSRC, "mdc_jenc.hip")
+JENC_EXPORT_MAP = os.path.join(CSRC, "mdc_jenc_exports.map")
+
+
+def build_jenc(force=False):
+    """libmdc_jenc.so: the device baseline JPEG encoder (include/mdc_jenc.h) -- one translation unit, independent of libmdc_hip.so
+    and outside its build identity."""
+    if force or _stale(LIB_JENC, [JENC_SOURCE, os.path.join(INC, "mdc_jenc.h"), JENC_EXPORT_MAP]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, JENC_SOURCE, "-Wl,--version-script=" + JENC_EXPORT_MAP, "-o", LIB_JENC])
+    return LIB_JENC
 
 
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")
@@ -287,6 +310,7 @@ def build_all(force=False):
     build_programs(force)
     build_multi(force)
     build_bench(force)
+    build_jenc(force)
     build_debug()
     build_fault_injection()
     return LIB_HIP, LIB_HOST, LIB_MULTI

@@ -271,12 +271,24 @@ BENCH_API = {  # include/mdc_bench.h (libmdc_bench.so; not the product ABI)
     "mdcb_alias_free": (_i, [_i, _vp, _i64, _i]),
     "mdcb_chunked_alloc": (_i, [_i, _i64, _i, _i, _P(_vp)]),
 }
+JENC_API = {  # include/mdc_jenc.h (libmdc_jenc.so: the device JPEG encoder, a library of its own)
+    "mdcj_jpeg_bound": (_i64, [_i, _i]),
+    "mdcj_last_error": (_cp, []),
+    "mdcj_create": (_i, [_i, _i, _i, _i, _i, _P(_vp)]),
+    "mdcj_destroy": (None, [_vp]),
+    "mdcj_encode_f32_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcj_encode_u8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcj_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
+    "mdcj_fetch": (_i64, [_vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
+LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
 _hip = None
 _host = None
 _bench = None
+_jenc = None
 
 
 def _share_hip_runtime_with_torch():
@@ -321,6 +333,15 @@ def bench_lib():
         _share_hip_runtime_with_torch()
         _bench = _load(LIB_BENCH_PATH, BENCH_API)
     return _bench
+
+
+def jenc_lib():
+    """libmdc_jenc.so: the baseline JPEG encoder for device-resident frames (include/mdc_jenc.h)."""
+    global _jenc
+    if _jenc is None:
+        _share_hip_runtime_with_torch()
+        _jenc = _load(LIB_JENC_PATH, JENC_API)
+    return _jenc
 
 
 def hip_lib():
@@ -977,6 +998,67 @@ class PhotometricUndistorter:
 
     def unmap(self, img_u8, out_f32, g, v, o):
         self._L.mdch_photo_unmap(self._h, _np_ptr(img_u8), _np_ptr(out_f32), img_u8.size, int(g), int(v), int(o))
+
+
+class JpegEncoder:
+    """One mdcj_encoder (include/mdc_jenc.h): device-resident w x h frames -> one baseline JFIF file per frame, the bytes
+    libjpeg writes at `quality`.  encode() fills device slots (the encoder's own unless d_out / d_sizes are given) and returns
+    (d_out, sizes); files() brings the encoded bytes, and only those, to the host."""
+
+    def __init__(self, w, h, quality=95, max_frames=1, device=-1):
+        self._L = jenc_lib()
+        self.w, self.h, self.quality, self.max_frames = int(w), int(h), int(quality), int(max_frames)
+        h_ = _vp()
+        self._check(self._L.mdcj_create(int(device), self.w, self.h, self.quality, self.max_frames, C.byref(h_)))
+        self._h = h_
+        self.bound = int(self._L.mdcj_jpeg_bound(self.w, self.h))
+        self._own = None
+        self._last = None
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MdcError(int(rc), self._L.mdcj_last_error().decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mdcj_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def output(self):
+        """(d_out, slot_bytes, d_sizes): the encoder's own output arrays, max_frames slots of `bound` bytes"""
+        if self._own is None:
+            o, n, z = _vp(), _i64(), _vp()
+            self._check(self._L.mdcj_output_device(self._h, C.byref(o), C.byref(n), C.byref(z)))
+            self._own = (o.value, n.value, z.value)
+        return self._own
+
+    def encode(self, d_frames, nframes, frame_stride=None, u8=False, d_out=None, slot_bytes=None, d_sizes=None, stream=0):
+        """d_frames: device address of nframes float32 (u8: uint8) frames, frame_stride elements apart (default w * h).
+        -> (d_out, sizes): the device address of the slots (slot_bytes apart) and the files' lengths as a numpy array."""
+        if d_out is None:
+            d_out, slot_bytes, d_sizes = self.output()
+        fn = self._L.mdcj_encode_u8_device if u8 else self._L.mdcj_encode_f32_device
+        stride = self.w * self.h if frame_stride is None else int(frame_stride)
+        self._check(fn(self._h, d_frames, stride, int(nframes), d_out, int(slot_bytes), d_sizes, _stream(stream)))
+        sizes = np.zeros(int(nframes), np.int32)
+        self._check(self._L.mdcj_fetch(self._h, d_out, int(slot_bytes), d_sizes, int(nframes), None, 0, _np_ptr(sizes), _stream(stream)))
+        self._last = (d_out, int(slot_bytes), d_sizes, int(nframes), stream)
+        return d_out, sizes
+
+    def files(self):
+        """the files of the last encode() as a list of bytes objects"""
+        if self._last is None:
+            raise MdcError(ERR_STATE, "JpegEncoder.files: nothing has been encoded")
+        d_out, slot_bytes, d_sizes, nframes, stream = self._last
+        sizes = np.zeros(nframes, np.int32)
+        total = self._check(self._L.mdcj_fetch(self._h, d_out, slot_bytes, d_sizes, nframes, None, 0, _np_ptr(sizes), _stream(stream)))
+        buf = np.zeros(max(int(total), 1), np.uint8)
+        self._check(self._L.mdcj_fetch(self._h, d_out, slot_bytes, d_sizes, nframes, _np_ptr(buf), buf.size, _np_ptr(sizes), _stream(stream)))
+        at = np.concatenate([[0], np.cumsum(sizes)])
+        return [buf[at[i]:at[i + 1]].tobytes() for i in range(nframes)]
 
 
 def decode_gray8(data):
