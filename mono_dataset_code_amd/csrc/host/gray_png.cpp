@@ -1,4 +1,5 @@
 #include "gray_png.h"
+#include "image_codecs.h"
 #include "image_codecs_internal.h"
 
 #include <zlib.h>
@@ -8,19 +9,6 @@
 
 namespace mdc_host {
 namespace {
-
-bool slurp(const std::string& path, std::vector<unsigned char>& buf) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  fseek(f, 0, SEEK_END);
-  long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  if (n < 0) { fclose(f); return false; }
-  buf.resize((size_t)n);
-  bool ok = n == 0 || fread(buf.data(), 1, (size_t)n, f) == (size_t)n;
-  fclose(f);
-  return ok;
-}
 
 GrayImage decode_png(const std::vector<unsigned char>& buf) {
   GrayImage none;
@@ -55,7 +43,7 @@ GrayImage decode_pgm(const std::vector<unsigned char>& buf) {
 
 GrayImage read_gray_image(const std::string& path) {
   std::vector<unsigned char> buf;
-  if (!slurp(path, buf) || buf.size() < 16) return GrayImage();
+  if (!read_file(path, buf) || buf.size() < 16) return GrayImage();
   static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   if (!memcmp(buf.data(), sig, 8)) return decode_png(buf);
   buf.push_back(0);

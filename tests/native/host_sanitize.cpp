@@ -19,6 +19,7 @@
 #include "image_codecs_internal.h"
 #include "mdc_hip.h"
 #include "mdc_host.h"
+#include "pool_batch_case.h"
 #include "zip_reader.h"
 
 static std::vector<std::string> list(const std::string& dir) {
@@ -132,6 +133,15 @@ int main(int argc, char** argv) {
     delete img;
     ExposureImage* out[4] = {0, 0, 0, 0};
     (void)reader.getImages(0, n < 4 ? n : 4, true, true, true, true, out);
+  }
+  // 5. the decode pool on its own in getImages' pattern: lanes that wait on sub-ranges, one ends early, the storage dies after the wait
+  {
+    const struct { const char* seq; int bad_frame; } cases[] = {{"seq_png", 3}, {"seq_zip_jpg", -1}, {"seq_zip_badsize", 5}};
+    for (const auto& c : cases)
+      if (pool_batch_case(root + "/sequences/" + c.seq + "/", 300, c.bad_frame) < 0) {
+        std::printf("decode pool, batch pattern, %s: a frame decoded that must not, or the other way round\n", c.seq);
+        return 1;
+      }
   }
   {
     ExposureImage a(33, 17, 1.0, 2.0f, 3);

@@ -4,7 +4,9 @@
 //     while prefetches are in flight;
 //   * several readers on one folder, each on its own thread;
 //   * the ExposureImage pool hammered from several threads (slabs created, blocks reused, trimmed concurrently);
-//   * the frame decoders and mdch_jpeg_stream called concurrently on shared input bytes.
+//   * the frame decoders and mdch_jpeg_stream called concurrently on shared input bytes;
+//   * the decode pool on its own in getImages' pattern (pool_batch_case.h): two lane threads submitting chunked ranges and waiting on
+//     sub-ranges, one of them ending early with requests queued, the owner waiting for the set to go idle before its storage dies.
 // No GPU work: this runs on the CPU-only test host; the HIP side has its own thread tests (tests/native/thread_soak.cpp).
 // usage: host_tsan <fixture root made by the test>
 #include <atomic>
@@ -19,6 +21,7 @@
 #include "image_codecs_internal.h"
 #include "mdc_hip.h"
 #include "mdc_host.h"
+#include "pool_batch_case.h"
 
 static long walk(const std::string& dir, int rounds, int threads, int prefetch) {
   DatasetReader reader(dir);
@@ -108,6 +111,17 @@ int main(int argc, char** argv) {
       });
     for (auto& x : th) x.join();
     total += sum.load();
+  }
+  {
+    const struct { const char* seq; int bad_frame; } cases[] = {{"seq_png", 3}, {"seq_zip_jpg", -1}, {"seq_zip_badsize", 5}};
+    for (const auto& c : cases) {
+      const long sum = pool_batch_case(root + "/sequences/" + c.seq + "/", 300, c.bad_frame);
+      if (sum < 0) {
+        std::printf("decode pool, batch pattern, %s: a frame decoded that must not, or the other way round\n", c.seq);
+        return 1;
+      }
+      total += sum;
+    }
   }
   std::printf("HOST_TSAN_OK %ld\n", total);
   return 0;

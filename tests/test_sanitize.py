@@ -151,7 +151,8 @@ def test_host_layer_under_asan_ubsan(tmp_path):
 def test_host_threads_under_tsan(tmp_path):
     """ThreadSanitizer over the host layer's threads (tests/native/host_tsan.cpp): the reader's decode pool with the caller
     consuming, jumping, resizing the pool and dying with prefetches in flight; four readers on four threads; the ExposureImage
-    pool from eight threads with a concurrent trim; the decoders and mdch_jpeg_stream on shared input."""
+    pool from eight threads with a concurrent trim; the decoders and mdch_jpeg_stream on shared input; the decode pool on its own
+    in getImages' pattern (tests/native/pool_batch_case.h, also run under ASan / UBSan by the test above)."""
     from mono_dataset_code_amd import build
 
     probe = tmp_path / "probe.cpp"

@@ -3,7 +3,7 @@
 the reference reader as shipped (CPU, one thread), the reference's unmodified reader on this repo's drop-in classes,
 this repo's reader frame by frame (getImage) and batched (getImages), from an images/ folder of PNGs, from a zip of
 PNGs and from a zip of JPEGs (MDC_RATE_KINDS=folder_png,zip_png,zip_jpg; also zip_jpg_rst: restart intervals, zip_jpg_420 /
-zip_jpg_444: colour files).  usage: python tools/reader_rate.py [frames] (default 256)"""
+zip_jpg_444: colour files; MDC_RATE_BIN: the folder of the reader_rate_* programs, for one linked against another build).  usage: python tools/reader_rate.py [frames] (default 256)"""
 import io
 import os
 import subprocess
@@ -19,7 +19,7 @@ from PIL import Image  # noqa: E402
 from mono_dataset_code_amd import synth  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-BIN = os.path.join(ROOT, "oracle", "_ref")
+BIN = os.environ.get("MDC_RATE_BIN") or os.path.join(ROOT, "oracle", "_ref")
 
 
 def textured(seed):
