@@ -198,13 +198,17 @@ RESPONSE_CALIB = os.path.join(BIN, "responseCalib")
 RESPONSE_CALIB_SOURCE = os.path.join(CSRC, "programs", "responseCalib.cpp")
 PLAY_DATASET = os.path.join(BIN, "playDataset")
 PLAY_DATASET_SOURCE = os.path.join(CSRC, "programs", "playDataset.cpp")
+RECTIFY_DATASET = os.path.join(BIN, "rectifyDataset")
+RECTIFY_DATASET_SOURCE = os.path.join(CSRC, "programs", "rectifyDataset.cpp")
 
 
 def build_programs(force=False):
     """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so;
-    bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so."""
+    bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so;
+    bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those and libmdc_zipw.so."""
     build_host(force)
     build_jenc(force)
+    build_zipw(force)
     os.makedirs(BIN, exist_ok=True)
     deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RESPONSE_CALIB, deps):
@@ -215,6 +219,11 @@ def build_programs(force=False):
     if force or _stale(PLAY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
               PLAY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-Wl,-rpath,$ORIGIN/..", "-o", PLAY_DATASET])
+    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_ZIPW, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
+            os.path.join(INC, "mdc_zipw.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
+    if force or _stale(RECTIFY_DATASET, deps):
+        _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
+              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_zipw", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
     return RESPONSE_CALIB
 
 
@@ -242,6 +251,20 @@ def build_jenc(force=False):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, JENC_SOURCE, "-Wl,--version-script=" + JENC_EXPORT_MAP, "-o", LIB_JENC])
     return LIB_JENC
+
+
+LIB_ZIPW = os.path.join(PKG, "libmdc_zipw.so")
+ZIPW_SOURCE = os.path.join(CSRC, "mdc_zipw.hip")
+ZIPW_EXPORT_MAP = os.path.join(CSRC, "mdc_zipw_exports.map")
+
+
+def build_zipw(force=False):
+    """libmdc_zipw.so: ZIP archives of device-resident files, checksummed and laid out on the device (include/mdc_zipw.h) -- one
+    translation unit, independent of every other library here and outside libmdc_hip.so's build identity."""
+    if force or _stale(LIB_ZIPW, [ZIPW_SOURCE, os.path.join(INC, "mdc_zipw.h"), ZIPW_EXPORT_MAP]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, ZIPW_SOURCE, "-Wl,--version-script=" + ZIPW_EXPORT_MAP, "-o", LIB_ZIPW])
+    return LIB_ZIPW
 
 
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")
@@ -314,6 +337,7 @@ def build_all(force=False):
     build_multi(force)
     build_bench(force)
     build_jenc(force)
+    build_zipw(force)
     build_debug()
     build_fault_injection()
     return LIB_HIP, LIB_HOST, LIB_MULTI

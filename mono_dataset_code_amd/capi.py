@@ -281,14 +281,29 @@ JENC_API = {  # include/mdc_jenc.h (libmdc_jenc.so: the device JPEG encoder, a l
     "mdcj_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
     "mdcj_fetch": (_i64, [_vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
 }
+ZIPW_API = {  # include/mdc_zipw.h (libmdc_zipw.so: ZIP archives of device-resident files, a library of its own)
+    "mdcz_last_error": (_cp, []),
+    "mdcz_crc_geometry": (None, [_i64, _i64, _P(_i64)]),
+    "mdcz_crc32_device": (_i, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "mdcz_crc32_variant_device": (_i, [_i, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "mdcz_segment_bound": (_i64, [_i64, _i64, _i]),
+    "mdcz_segment_device": (_i, [_vp, _i64, _vp, _vp, _i64, _i64, _cp, _vp, _i64, _vp, _vp]),
+    "mdcz_directory": (_i64, [_vp, _i64, _vp, _i64, _i64, _vp, _i64]),
+    "mdcz_open": (_i, [_cp, _i, _i64, _P(_vp)]),
+    "mdcz_append_device": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _cp, _vp]),
+    "mdcz_close": (_i64, [_vp]),
+    "mdcz_abort": (None, [_vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
 LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
+LIB_ZIPW_PATH = os.path.join(_PKG, "libmdc_zipw.so")
 _hip = None
 _host = None
 _bench = None
 _jenc = None
+_zipw = None
 
 
 def _share_hip_runtime_with_torch():
@@ -342,6 +357,15 @@ def jenc_lib():
         _share_hip_runtime_with_torch()
         _jenc = _load(LIB_JENC_PATH, JENC_API)
     return _jenc
+
+
+def zipw_lib():
+    """libmdc_zipw.so: CRC-32, ZIP segments and the archive writer for device-resident files (include/mdc_zipw.h)."""
+    global _zipw
+    if _zipw is None:
+        _share_hip_runtime_with_torch()
+        _zipw = _load(LIB_ZIPW_PATH, ZIPW_API)
+    return _zipw
 
 
 def hip_lib():
@@ -1059,6 +1083,86 @@ class JpegEncoder:
         self._check(self._L.mdcj_fetch(self._h, d_out, slot_bytes, d_sizes, nframes, _np_ptr(buf), buf.size, _np_ptr(sizes), _stream(stream)))
         at = np.concatenate([[0], np.cumsum(sizes)])
         return [buf[at[i]:at[i + 1]].tobytes() for i in range(nframes)]
+
+
+ZIPW_RECORD = np.dtype([("offset", "<i8"), ("crc", "<u4"), ("size", "<u4")])  # mdcz_record
+ZIPW_NAME_STRIDE = 40  # MDCZ_NAME_STRIDE
+
+
+def _zipw_check(rc):
+    if rc < 0:
+        raise MdcError(int(rc), zipw_lib().mdcz_last_error().decode())
+    return rc
+
+
+def crc32_geometry(slot_bytes, nfiles):
+    """(bytes per load, a lane's stride, a wave's span, a workgroup's span, parts per file) of the checksum kernel for such a call"""
+    out = (_i64 * 5)()
+    zipw_lib().mdcz_crc_geometry(int(slot_bytes), int(nfiles), out)
+    return tuple(int(v) for v in out)
+
+
+def crc32_device(d_data, slot_bytes, d_sizes, nfiles, d_crc, stream=None, variant=0):
+    """zlib's crc32 of nfiles device-resident byte strings (file f: d_sizes[f] bytes at d_data + f * slot_bytes) into the uint32
+    device array d_crc; enqueued on `stream`, not synchronised.  All arguments are device addresses given as integers."""
+    L = zipw_lib()
+    if variant:
+        _zipw_check(L.mdcz_crc32_variant_device(int(variant), d_data, int(slot_bytes), d_sizes, int(nfiles), d_crc, _stream(stream)))
+    else:
+        _zipw_check(L.mdcz_crc32_device(d_data, int(slot_bytes), d_sizes, int(nfiles), d_crc, _stream(stream)))
+
+
+def zip_directory(records, names, segment_base_offset=0, directory_offset=0):
+    """mdcz_directory on a ZIPW_RECORD array and a list of names (bytes) -> the central directory and end records as bytes"""
+    L = zipw_lib()
+    records = np.ascontiguousarray(records, dtype=ZIPW_RECORD)
+    table = np.zeros((max(len(names), 1), ZIPW_NAME_STRIDE), np.uint8)
+    for i, name in enumerate(names):
+        if len(name) >= ZIPW_NAME_STRIDE:
+            raise MdcError(ERR_ARG, "zip_directory: name %d has %d bytes, at most %d fit" % (i, len(name), ZIPW_NAME_STRIDE - 1))
+        table[i, :len(name)] = np.frombuffer(bytes(name), np.uint8)
+    n = len(records)
+    need = _zipw_check(L.mdcz_directory(_np_ptr(records), n, _np_ptr(table), int(segment_base_offset), int(directory_offset), None, 0))
+    out = np.zeros(max(int(need), 1), np.uint8)
+    got = _zipw_check(L.mdcz_directory(_np_ptr(records), n, _np_ptr(table), int(segment_base_offset), int(directory_offset), _np_ptr(out), out.size))
+    return out[:got].tobytes()
+
+
+class ZipWriter:
+    """One mdcz_writer (include/mdc_zipw.h): an archive of stored entries at `path`, fed with batches of device-resident files.
+    append() checksums, lays out and gathers a batch on the device and writes its segment; close() adds the central directory and
+    returns the archive's size.  staging_cap (bytes, 0 = the library's default) is where the writer splits a batch."""
+
+    def __init__(self, path, device=0, staging_cap=0):
+        self._L = zipw_lib()
+        h_ = _vp()
+        _zipw_check(self._L.mdcz_open(os.fsencode(path), int(device), int(staging_cap), C.byref(h_)))
+        self._h = h_
+
+    def append(self, d_data, slot_bytes, d_sizes, nfiles, first_index=0, suffix=".jpg", valid=None, stream=None):
+        """valid: host array of nfiles flags (None = every file); entry names are first_index + f as %05d, then suffix"""
+        if not getattr(self, "_h", None):
+            raise MdcError(ERR_STATE, "ZipWriter.append: the writer is closed")
+        if valid is not None:
+            valid = np.ascontiguousarray(valid, dtype=np.uint8)
+            if valid.size != int(nfiles):
+                raise MdcError(ERR_ARG, "ZipWriter.append: %d flags for %d files" % (valid.size, int(nfiles)))
+        sfx = suffix if isinstance(suffix, bytes) else suffix.encode("latin-1")
+        _zipw_check(self._L.mdcz_append_device(self._h, d_data, int(slot_bytes), d_sizes, _np_ptr(valid), int(nfiles), int(first_index), sfx, _stream(stream)))
+
+    def close(self):
+        """-> the archive's size in bytes (None when already closed)"""
+        if getattr(self, "_h", None):
+            h_, self._h = self._h, None
+            return int(_zipw_check(self._L.mdcz_close(h_)))
+        return None
+
+    def abort(self):
+        if getattr(self, "_h", None):
+            self._L.mdcz_abort(self._h)
+            self._h = None
+
+    __del__ = abort
 
 
 def decode_gray8(data):
