@@ -27,10 +27,10 @@ HIP_SOURCES = [os.path.join(CSRC, f) for f in ("mdc_kernels.hip", "mdc_vcal.hip"
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "mdc_exports.map"), os.path.join(CSRC, "mdc_internal.h"), os.path.join(CSRC, "mdc_ctx.h"), os.path.join(CSRC, "mdc_build_config.h"), os.path.join(CSRC, "fov_point_model.h"), os.path.join(CSRC, "placement_classes.h"), os.path.join(INC, "mdc_hip.h")]
 HOST_SOURCES = [os.path.join(HOST, f) for f in (
     "fov_undistorter.cpp", "photometric_undistorter.cpp", "gray_png.cpp", "host_device.cpp", "mdc_host_capi.cpp",
-    "image_codecs.cpp", "image_codecs_ext.cpp", "zip_reader.cpp", "image_pool.cpp", "frame_source.cpp", "decode_pool.cpp",
+    "image_codecs.cpp", "image_codecs_png.cpp", "image_codecs_jpeg.cpp", "image_codecs_jpeg_stream.cpp", "zip_reader.cpp", "image_pool.cpp", "frame_source.cpp", "decode_pool.cpp",
     "prefetch_cache.cpp", "device_lanes.cpp", "batch_run.cpp", "dataset_reader.cpp")]
 HOST_DEPS = HOST_SOURCES + [os.path.join(HOST, "mdc_host_exports.map"), os.path.join(HOST, "gray_png.h"), os.path.join(HOST, "host_device.h"),
-                            os.path.join(HOST, "image_codecs.h"), os.path.join(HOST, "image_codecs_internal.h"), os.path.join(HOST, "zip_reader.h"),
+                            os.path.join(HOST, "image_codecs.h"), os.path.join(HOST, "image_codecs_internal.h"), os.path.join(HOST, "image_codecs_jpeg.h"), os.path.join(HOST, "zip_reader.h"),
                             os.path.join(HOST, "frame_source.h"), os.path.join(HOST, "decode_pool.h"), os.path.join(HOST, "prefetch_cache.h"),
                             os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"),
                             os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h"),

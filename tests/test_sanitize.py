@@ -35,7 +35,7 @@ def make_fixtures(tmp_path):
     open(root / "images_any" / "h.pgm", "wb").write(b"P5\n# c\n90 70\n255\n" + img.tobytes())
     open(root / "images_any" / "i.pgm", "wb").write(b"P5 99999 99999 255\n" + bytes(100))
     open(root / "images_any" / "j.bin", "wb").write(os.urandom(3000))
-    # the extended decoders (image_codecs_ext.cpp): every PNG flavour, Adam7, progressive JPEG -- sound, truncated and bit-flipped
+    # the less common inputs (image_codecs_png.cpp, image_codecs_jpeg.cpp): every PNG flavour, Adam7, progressive JPEG -- sound, truncated and bit-flipped
     from test_reader_cpu import interlaced_png, png_bytes, raw_png
 
     rgb = np.stack([img, img[::-1], 255 - img], -1)
