@@ -205,10 +205,12 @@ RECTIFY_DATASET_SOURCE = os.path.join(CSRC, "programs", "rectifyDataset.cpp")
 def build_programs(force=False):
     """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so;
     bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so;
-    bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those and libmdc_zipw.so."""
+    bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those, libmdc_zipw.so
+    and libmdc_pngw.so."""
     build_host(force)
     build_jenc(force)
     build_zipw(force)
+    build_pngw(force)
     os.makedirs(BIN, exist_ok=True)
     deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RESPONSE_CALIB, deps):
@@ -219,11 +221,11 @@ def build_programs(force=False):
     if force or _stale(PLAY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
               PLAY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-Wl,-rpath,$ORIGIN/..", "-o", PLAY_DATASET])
-    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_ZIPW, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
-            os.path.join(INC, "mdc_zipw.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
+    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_ZIPW, LIB_PNGW, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
+            os.path.join(INC, "mdc_zipw.h"), os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RECTIFY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
-              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_zipw", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
+              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_zipw", "-lmdc_pngw", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
     return RESPONSE_CALIB
 
 
@@ -265,6 +267,21 @@ def build_zipw(force=False):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, ZIPW_SOURCE, "-Wl,--version-script=" + ZIPW_EXPORT_MAP, "-o", LIB_ZIPW])
     return LIB_ZIPW
+
+
+LIB_PNGW = os.path.join(PKG, "libmdc_pngw.so")
+PNGW_SOURCE = os.path.join(CSRC, "mdc_pngw.hip")
+PNGW_EXPORT_MAP = os.path.join(CSRC, "mdc_pngw_exports.map")
+
+
+def build_pngw(force=False):
+    """libmdc_pngw.so: the device PNG encoder (include/mdc_pngw.h) -- one translation unit on top of libmdc_zipw.so (for the IDAT
+    chunk's CRC-32), independent of libmdc_hip.so and outside its build identity."""
+    build_zipw(force)
+    if force or _stale(LIB_PNGW, [PNGW_SOURCE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_zipw.h"), PNGW_EXPORT_MAP, LIB_ZIPW]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGW_EXPORT_MAP, "-o", LIB_PNGW])
+    return LIB_PNGW
 
 
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")
@@ -338,6 +355,7 @@ def build_all(force=False):
     build_bench(force)
     build_jenc(force)
     build_zipw(force)
+    build_pngw(force)
     build_debug()
     build_fault_injection()
     return LIB_HIP, LIB_HOST, LIB_MULTI

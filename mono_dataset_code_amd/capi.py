@@ -294,16 +294,29 @@ ZIPW_API = {  # include/mdc_zipw.h (libmdc_zipw.so: ZIP archives of device-resid
     "mdcz_close": (_i64, [_vp]),
     "mdcz_abort": (None, [_vp]),
 }
+PNGW_API = {  # include/mdc_pngw.h (libmdc_pngw.so: the device PNG encoder, a library of its own on top of libmdc_zipw.so)
+    "mdcp_png_bound": (_i64, [_i, _i, _i]),
+    "mdcp_last_error": (_cp, []),
+    "mdcp_create": (_i, [_i, _i, _i, _i, _i, _i, _P(_vp)]),
+    "mdcp_destroy": (None, [_vp]),
+    "mdcp_encode_u8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcp_encode_u16_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcp_encode_f32_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcp_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
+    "mdcp_huffman_lengths_device": (_i, [_vp, _i, _i, _vp, _vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
 LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
 LIB_ZIPW_PATH = os.path.join(_PKG, "libmdc_zipw.so")
+LIB_PNGW_PATH = os.path.join(_PKG, "libmdc_pngw.so")
 _hip = None
 _host = None
 _bench = None
 _jenc = None
 _zipw = None
+_pngw = None
 
 
 def _share_hip_runtime_with_torch():
@@ -366,6 +379,15 @@ def zipw_lib():
         _share_hip_runtime_with_torch()
         _zipw = _load(LIB_ZIPW_PATH, ZIPW_API)
     return _zipw
+
+
+def pngw_lib():
+    """libmdc_pngw.so: the PNG encoder for device-resident grayscale images (include/mdc_pngw.h)."""
+    global _pngw
+    if _pngw is None:
+        _share_hip_runtime_with_torch()
+        _pngw = _load(LIB_PNGW_PATH, PNGW_API)
+    return _pngw
 
 
 def hip_lib():
@@ -1083,6 +1105,60 @@ class JpegEncoder:
         self._check(self._L.mdcj_fetch(self._h, d_out, slot_bytes, d_sizes, nframes, _np_ptr(buf), buf.size, _np_ptr(sizes), _stream(stream)))
         at = np.concatenate([[0], np.cumsum(sizes)])
         return [buf[at[i]:at[i + 1]].tobytes() for i in range(nframes)]
+
+
+PNG_FILTER_ADAPTIVE = 5  # MDCP_FILTER_ADAPTIVE
+
+
+class PngEncoder:
+    """One mdcp_encoder (include/mdc_pngw.h): device-resident w x h grayscale images of `depth` bits -> one PNG file per image
+    (filtered, Huffman-only DEFLATE with a stored fallback).  encode() fills device slots (the encoder's own unless d_out /
+    d_sizes are given) in the layout ZipWriter.append() takes and returns their device addresses; it does not synchronise."""
+
+    def __init__(self, w, h, depth=8, filter=PNG_FILTER_ADAPTIVE, max_images=1, device=-1):
+        self._L = pngw_lib()
+        self.w, self.h, self.depth, self.filter, self.max_images = int(w), int(h), int(depth), int(filter), int(max_images)
+        h_ = _vp()
+        self._check(self._L.mdcp_create(int(device), self.w, self.h, self.depth, self.filter, self.max_images, C.byref(h_)))
+        self._h = h_
+        self.bound = int(self._L.mdcp_png_bound(self.w, self.h, self.depth))
+        self._own = None
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MdcError(int(rc), self._L.mdcp_last_error().decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mdcp_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def output(self):
+        """(d_out, slot_bytes, d_sizes): the encoder's own output arrays, max_images slots of `bound` bytes"""
+        if self._own is None:
+            o, n, z = _vp(), _i64(), _vp()
+            self._check(self._L.mdcp_output_device(self._h, C.byref(o), C.byref(n), C.byref(z)))
+            self._own = (o.value, n.value, z.value)
+        return self._own
+
+    def encode(self, d_images, nimages, kind="u8", stride=None, d_out=None, slot_bytes=None, d_sizes=None, stream=0):
+        """d_images: device address of nimages images of `kind` ("u8", "u16" or "f32"), stride elements apart (default w * h).
+        -> (d_out, slot_bytes, d_sizes), device addresses."""
+        if d_out is None:
+            d_out, slot_bytes, d_sizes = self.output()
+        fn = {"u8": self._L.mdcp_encode_u8_device, "u16": self._L.mdcp_encode_u16_device, "f32": self._L.mdcp_encode_f32_device}[kind]
+        self._check(fn(self._h, d_images, self.w * self.h if stride is None else int(stride), int(nimages), d_out, int(slot_bytes), d_sizes, _stream(stream)))
+        return d_out, int(slot_bytes), d_sizes
+
+
+def huffman_lengths_device(d_hist, nsym, limit, d_lengths, stream=None):
+    """mdcp_huffman_lengths_device: the encoder's code builder on nsym uint32 counts -> nsym uint8 lengths (device addresses)"""
+    L = pngw_lib()
+    if L.mdcp_huffman_lengths_device(d_hist, int(nsym), int(limit), d_lengths, _stream(stream)) < 0:
+        raise MdcError(ERR_ARG, L.mdcp_last_error().decode())
 
 
 ZIPW_RECORD = np.dtype([("offset", "<i8"), ("crc", "<u4"), ("size", "<u4")])  # mdcz_record

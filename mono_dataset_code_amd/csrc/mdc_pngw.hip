@@ -1,0 +1,798 @@
+// libmdc_pngw.so (include/mdc_pngw.h): PNG files of device-resident grayscale images, made on the device.  One translation unit;
+// the only thing it takes from elsewhere is mdcz_crc32_device (libmdc_zipw.so) for the IDAT chunk's CRC.
+//
+// One call is six kernels and the checksum, with no host round trip between them:
+//   pngw_filter_kernel   16 rows per workgroup, one wave per row: the row's filter type (adaptive: all five sums first), the filtered
+//                        bytes into the scratch array, their histogram (one LDS histogram per wave, flushed with integer atomics)
+//                        and the Adler-32 partial sums (sum d and, reduced mod 65521 per row and lane, sum (F - i) d; 64-bit atomics).
+//   pngw_build_kernel    one workgroup per image: the symbols ranked by (count, symbol) by all lanes, then lane 0 alone: code lengths,
+//                        canonical codes (stored bit-reversed: the stream is LSB-first), the run-length coded header and its bits,
+//                        the dynamic stream's length and the stored/dynamic decision.  build_block() is plain C++ (host and device).
+//   pngw_scan_kernel     one workgroup per image: each lane sums the code lengths of 16 filtered bytes (one 16-byte load, consecutive
+//                        lanes on consecutive words), a scan gives every such unit its 64-bit bit offset; the words of the output
+//                        that the pack kernel will OR into are cleared here.
+//   pngw_pack_kernel     a lane packs its unit's codes at its bit offset: its first and last word, shared with the neighbours, by
+//                        atomicOr, the words in between by plain stores.  The bit stream starts at byte 43 of the file, at any
+//                        alignment: words are counted from the 4-byte boundary at or below it and every offset carries that shift.
+//                        A stored image is a byte gather with the 5-byte block headers instead.
+//   pngw_finish_kernel   signature, IHDR, IDAT length and tag, zlib header, Adler-32, IEND, d_sizes[f]; then mdcz_crc32_device over
+//                        tag + data, and pngw_crc_kernel puts the four bytes in.
+#include "../../include/mdc_pngw.h"
+
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <new>
+
+#include "../../include/mdc_zipw.h"
+
+#define PNGW_HD __host__ __device__ __forceinline__
+
+namespace {
+
+constexpr int kMaxSym = MDCP_MAX_SYMBOLS;
+constexpr int kLit = 257;            // literals and end-of-block
+constexpr int kSeq = 258;            // code lengths in the header: 257 + one distance code
+constexpr int kHdrWords = 128;       // 17 + 57 + 258 * 14 bits at most: 116 words
+constexpr int kZeroWords = 296;      // per image, cleared per call: histogram [288], Adler sums as two 64-bit words
+constexpr int kTabWords = 400;       // per image: codes [260], header words [128], meta [12]
+constexpr int kMeta = 388;           // meta: 0 stored?, 1 header bits, 2 stream bytes, 3/4 data bits (low, high)
+constexpr int kStreamAt = 43;        // signature 8, IHDR 25, length 4, "IDAT" 4, zlib header 2
+constexpr int kRowsPerGroup = 16;
+constexpr int kMaxGrid = 8192;
+constexpr uint32_t kAdlerMod = 65521;
+constexpr long long kSmallBytes = 4 * (kZeroWords + kTabWords) + 8;  // + the checksum's length and result
+
+struct HuffWork {
+  unsigned long long wt[2 * kMaxSym];
+  uint16_t parent[2 * kMaxSym];
+  uint16_t depth[2 * kMaxSym];
+  uint16_t order[kMaxSym];
+  uint32_t count[16], next[16];
+};
+
+struct BuildLds {
+  uint32_t hist[kMaxSym];
+  uint8_t len[kMaxSym];
+  HuffWork work;
+  uint32_t codes[260];
+  uint8_t sym[kSeq + 2], ext[kSeq + 2];
+  uint32_t clhist[19];
+  uint8_t cllen[19];
+  uint32_t clcodes[19];
+  uint32_t hdr[kHdrWords];
+  uint32_t meta[12];
+};
+
+// order[r] = the used symbol of rank r by (count, symbol); lanes tid, tid + nthr, ... of the caller take their symbols
+PNGW_HD void huff_order(const uint32_t* hist, int nsym, uint16_t* order, int tid, int nthr) {
+  for (int s = tid; s < nsym; s += nthr) {
+    const uint32_t c = hist[s];
+    if (!c) continue;
+    int r = 0;
+    for (int j = 0; j < nsym; j++) {
+      const uint32_t o = hist[j];
+      r += (o && (o < c || (o == c && j < s))) ? 1 : 0;
+    }
+    order[r] = (uint16_t)s;
+  }
+}
+
+// include/mdc_pngw.h, "Code lengths"; k.order is filled
+PNGW_HD void huff_lengths(const uint32_t* hist, int nsym, int limit, HuffWork& k, uint8_t* len) {
+  int n = 0;
+  for (int s = 0; s < nsym; s++) {
+    len[s] = 0;
+    n += hist[s] ? 1 : 0;
+  }
+  if (n == 0) return;
+  if (n == 1) {
+    len[k.order[0]] = 1;
+    return;
+  }
+  for (int i = 0; i < n; i++) k.wt[i] = hist[k.order[i]];
+  int leaf = 0, inner = n, next = n;
+  while (next < 2 * n - 1) {
+    unsigned long long sum = 0;
+    for (int pick = 0; pick < 2; pick++) {
+      int node;
+      if (leaf < n && (inner >= next || k.wt[leaf] <= k.wt[inner])) node = leaf++;
+      else node = inner++;
+      sum += k.wt[node];
+      k.parent[node] = (uint16_t)next;
+    }
+    k.wt[next++] = sum;
+  }
+  k.depth[2 * n - 2] = 0;
+  for (int node = 2 * n - 3; node >= 0; node--) k.depth[node] = (uint16_t)(k.depth[k.parent[node]] + 1);
+  const uint32_t full = 1u << limit;
+  uint32_t kraft = 0;
+  for (int i = 0; i < n; i++) {
+    const int d = k.depth[i] < limit ? k.depth[i] : limit;
+    len[k.order[i]] = (uint8_t)d;
+    kraft += 1u << (limit - d);
+  }
+  while (kraft > full) {
+    bool any = false;
+    for (int i = 0; i < n && kraft > full; i++) {
+      const int s = k.order[i];
+      if (len[s] < limit) {
+        len[s]++;
+        kraft -= 1u << (limit - len[s]);
+        any = true;
+      }
+    }
+    if (!any) break;  // n > 2^limit: refused before the launch
+  }
+  while (kraft < full) {
+    const uint32_t room = full - kraft;
+    int i = n - 1;
+    while (i >= 0 && !(len[k.order[i]] > 1 && (1u << (limit - len[k.order[i]])) <= room)) i--;
+    if (i < 0) break;  // cannot happen for n >= 2 (the header's argument)
+    const int s = k.order[i];
+    kraft += 1u << (limit - len[s]);
+    len[s]--;
+  }
+}
+
+// codes[s] = the canonical code of symbol s, bit-reversed, | length << 16
+PNGW_HD void canonical(const uint8_t* len, int nsym, int limit, HuffWork& k, uint32_t* codes) {
+  for (int b = 0; b <= limit; b++) k.count[b] = 0;
+  for (int s = 0; s < nsym; s++) k.count[len[s]]++;
+  k.count[0] = 0;
+  uint32_t code = 0;
+  for (int b = 1; b <= limit; b++) {
+    code = (code + k.count[b - 1]) << 1;
+    k.next[b] = code;
+  }
+  for (int s = 0; s < nsym; s++) {
+    const int l = len[s];
+    uint32_t c = l ? k.next[l]++ : 0, r = 0;
+    for (int i = 0; i < l; i++) {
+      r = (r << 1) | (c & 1);
+      c >>= 1;
+    }
+    codes[s] = r | ((uint32_t)l << 16);
+  }
+}
+
+PNGW_HD void put_bits(uint32_t* words, uint32_t& nbits, uint32_t v, int n) {
+  const uint32_t at = nbits & 31;
+  words[nbits >> 5] |= v << at;
+  if (at + n > 32) words[(nbits >> 5) + 1] |= v >> (32 - at);
+  nbits += n;
+}
+
+PNGW_HD long long stored_bytes(long long F) { return F + 5 * ((F + 65534) / 65535); }
+
+// everything of one image's dynamic block that does not depend on the byte positions; L.hist[0..256] and L.work.order are filled
+PNGW_HD void build_block(BuildLds& L, long long F) {
+  huff_lengths(L.hist, kLit, 15, L.work, L.len);
+  canonical(L.len, kLit, 15, L.work, L.codes);
+  L.len[kLit] = 0;  // the one distance code
+  for (int i = 0; i < 19; i++) L.clhist[i] = 0;
+  int nsyms = 0;
+  for (int i = 0; i < kSeq;) {
+    const int v = L.len[i];
+    int run = 1;
+    while (i + run < kSeq && L.len[i + run] == v) run++;
+    i += run;
+    if (v == 0) {
+      while (run >= 11) {
+        const int n = run < 138 ? run : 138;
+        L.sym[nsyms] = 18, L.ext[nsyms++] = (uint8_t)(n - 11);
+        run -= n;
+      }
+      if (run >= 3) {
+        L.sym[nsyms] = 17, L.ext[nsyms++] = (uint8_t)(run - 3);
+        run = 0;
+      }
+    } else {
+      L.sym[nsyms] = (uint8_t)v, L.ext[nsyms++] = 0;
+      run--;
+      while (run >= 3) {
+        const int n = run < 6 ? run : 6;
+        L.sym[nsyms] = 16, L.ext[nsyms++] = (uint8_t)(n - 3);
+        run -= n;
+      }
+    }
+    for (; run > 0; run--) L.sym[nsyms] = (uint8_t)v, L.ext[nsyms++] = 0;
+  }
+  for (int i = 0; i < nsyms; i++) L.clhist[L.sym[i]]++;
+  huff_order(L.clhist, 19, L.work.order, 0, 1);
+  huff_lengths(L.clhist, 19, 7, L.work, L.cllen);
+  canonical(L.cllen, 19, 7, L.work, L.clcodes);
+  const uint8_t clorder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+  int hclen = 4;
+  for (int i = 4; i < 19; i++)
+    if (L.cllen[clorder[i]]) hclen = i + 1;
+  for (int i = 0; i < kHdrWords; i++) L.hdr[i] = 0;
+  uint32_t bits = 0;
+  put_bits(L.hdr, bits, 1, 1);  // BFINAL
+  put_bits(L.hdr, bits, 2, 2);  // BTYPE: dynamic
+  put_bits(L.hdr, bits, 0, 5);  // HLIT: 257 codes
+  put_bits(L.hdr, bits, 0, 5);  // HDIST: 1 code
+  put_bits(L.hdr, bits, (uint32_t)(hclen - 4), 4);
+  for (int i = 0; i < hclen; i++) put_bits(L.hdr, bits, L.cllen[clorder[i]], 3);
+  for (int i = 0; i < nsyms; i++) {
+    const int s = L.sym[i];
+    put_bits(L.hdr, bits, L.clcodes[s] & 0xffffu, (int)(L.clcodes[s] >> 16));
+    if (s >= 16) put_bits(L.hdr, bits, L.ext[i], s == 16 ? 2 : s == 17 ? 3 : 7);
+  }
+  unsigned long long data = 0;
+  for (int s = 0; s < 256; s++) data += (unsigned long long)L.hist[s] * L.len[s];
+  const unsigned long long total = bits + data + L.len[256];
+  const long long dyn = (long long)((total + 7) >> 3), stored = stored_bytes(F);
+  L.meta[0] = dyn < stored ? 0u : 1u;
+  L.meta[1] = bits;
+  L.meta[2] = (uint32_t)(dyn < stored ? dyn : stored);
+  L.meta[3] = (uint32_t)data;
+  L.meta[4] = (uint32_t)(data >> 32);
+}
+
+// ---------------------------------------------------------------------------------------------------- pixels -> filtered bytes
+
+__device__ __forceinline__ int sample_of(uint8_t v) { return v; }
+__device__ __forceinline__ int sample_of(uint16_t v) { return v; }
+__device__ __forceinline__ int sample_of(float v) {  // as mdcj_encode_f32_device: cv::Mat::convertTo(CV_8U)
+  const float r = fminf(fmaxf(rintf(v), 0.0f), 255.0f);
+  return v != v ? 0 : (int)r;
+}
+
+__device__ __forceinline__ int paeth(int a, int b, int c) {
+  const int p = a + b - c;
+  const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+__device__ __forceinline__ int filter_byte(int type, int x, int a, int b, int c) {
+  const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? ((a + b) >> 1) : paeth(a, b, c);
+  return (x - pred) & 255;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <typename T, int BPP>
+__global__ __launch_bounds__(256) void pngw_filter_kernel(const T* __restrict__ images, long long stride, long long nimages, int w, int h, int filter,
+                                                          uint8_t* __restrict__ filt, long long filt_stride, uint32_t* __restrict__ zeroed) {
+  __shared__ uint32_t hist[4][256];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long long groups = ((long long)h + kRowsPerGroup - 1) / kRowsPerGroup;
+  const long long items = nimages * groups;
+  const long long rs = 1 + (long long)w * BPP, F = rs * h;  // F < 2^31
+  for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+    const long long f = item / groups;
+    const int y0 = (int)(item - f * groups) * kRowsPerGroup;
+    const int y1 = y0 + kRowsPerGroup < h ? y0 + kRowsPerGroup : h;
+    for (int i = t; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    const T* __restrict__ img = images + f * stride;
+    uint8_t* __restrict__ out = filt + f * filt_stride;
+    unsigned long long s1 = 0, s2 = 0;
+    for (int y = y0 + wave; y < y1; y += 4) {
+      const T* __restrict__ row = img + (long long)y * w;
+      const T* __restrict__ up = row - w;  // read only when y > 0
+      int type = filter;
+      if (filter == MDCP_FILTER_ADAPTIVE) {
+        unsigned long long sum[5] = {0, 0, 0, 0, 0};
+        for (int x = lane; x < w; x += 64) {
+          const int X = sample_of(row[x]), A = x > 0 ? sample_of(row[x - 1]) : 0;
+          const int B = y > 0 ? sample_of(up[x]) : 0, Cc = (x > 0 && y > 0) ? sample_of(up[x - 1]) : 0;
+#pragma unroll
+          for (int k = 0; k < BPP; k++) {
+            const int sh = 8 * (BPP - 1 - k);
+            const int xb = (X >> sh) & 255, ab = (A >> sh) & 255, bb = (B >> sh) & 255, cb = (Cc >> sh) & 255;
+#pragma unroll
+            for (int ty = 0; ty < 5; ty++) {
+              const int d = filter_byte(ty, xb, ab, bb, cb);
+              sum[ty] += (unsigned)(d < 128 ? d : 256 - d);
+            }
+          }
+        }
+        unsigned long long best = 0;
+#pragma unroll
+        for (int ty = 0; ty < 5; ty++) {
+          const unsigned long long v = wave_sum(sum[ty]);
+          if (ty == 0 || v < best) best = v, type = ty;
+        }
+      }
+      const long long at = (long long)y * rs;
+      unsigned long long r2 = 0;
+      if (lane == 0) {
+        out[at] = (uint8_t)type;
+        atomicAdd(&hist[wave][type], 1u);
+        s1 += (unsigned)type;
+        r2 += (unsigned long long)(F - at) * (unsigned)type;
+      }
+      for (int x = lane; x < w; x += 64) {
+        const int X = sample_of(row[x]), A = x > 0 ? sample_of(row[x - 1]) : 0;
+        const int B = y > 0 ? sample_of(up[x]) : 0, Cc = (x > 0 && y > 0) ? sample_of(up[x - 1]) : 0;
+#pragma unroll
+        for (int k = 0; k < BPP; k++) {
+          const int sh = 8 * (BPP - 1 - k);
+          const int d = filter_byte(type, (X >> sh) & 255, (A >> sh) & 255, (B >> sh) & 255, (Cc >> sh) & 255);
+          const long long i = at + 1 + (long long)x * BPP + k;
+          out[i] = (uint8_t)d;
+          atomicAdd(&hist[wave][d], 1u);
+          s1 += (unsigned)d;
+          r2 += (unsigned long long)(F - i) * (unsigned)d;  // < 2^39 each, fewer than 2^12 per lane and row
+        }
+      }
+      s2 += r2 % kAdlerMod;
+    }
+    __syncthreads();
+    uint32_t* __restrict__ g = zeroed + f * kZeroWords;
+    const uint32_t v = hist[0][t] + hist[1][t] + hist[2][t] + hist[3][t];
+    if (v) atomicAdd(&g[t], v);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if (lane == 0 && y0 + wave < y1) {
+      unsigned long long* __restrict__ adler = (unsigned long long*)(g + kMaxSym);
+      atomicAdd(&adler[0], s1);
+      atomicAdd(&adler[1], s2);
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- the code
+
+__global__ __launch_bounds__(256) void pngw_build_kernel(long long nimages, long long F, const uint32_t* __restrict__ zeroed, uint32_t* __restrict__ tab) {
+  __shared__ BuildLds L;
+  const int t = threadIdx.x;
+  for (long long f = blockIdx.x; f < nimages; f += gridDim.x) {
+    L.hist[t] = zeroed[f * kZeroWords + t];
+    if (t == 0) L.hist[256] = 1;  // end-of-block
+    __syncthreads();
+    huff_order(L.hist, kLit, L.work.order, t, 256);
+    __syncthreads();
+    if (t == 0) build_block(L, F);
+    __syncthreads();
+    uint32_t* __restrict__ o = tab + f * kTabWords;
+    for (int i = t; i < kLit; i += 256) o[i] = L.codes[i];
+    if (t < kHdrWords) o[260 + t] = L.hdr[t];
+    if (t < 12) o[kMeta + t] = L.meta[t];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void pngw_lengths_kernel(const uint32_t* __restrict__ hist, int nsym, int limit, uint8_t* __restrict__ lengths) {
+  __shared__ BuildLds L;
+  const int t = threadIdx.x;
+  for (int s = t; s < nsym; s += 256) L.hist[s] = hist[s];
+  __syncthreads();
+  huff_order(L.hist, nsym, L.work.order, t, 256);
+  __syncthreads();
+  if (t == 0) huff_lengths(L.hist, nsym, limit, L.work, L.len);
+  __syncthreads();
+  for (int s = t; s < nsym; s += 256) lengths[s] = L.len[s];
+}
+
+// ---------------------------------------------------------------------------------------------------- bit offsets
+
+struct Slot {  // where an image's DEFLATE stream goes: 32-bit words from the 4-byte boundary at or below byte 43 of the file
+  uint8_t* stream;
+  uint32_t* words;
+  uint32_t shift;
+};
+
+__device__ __forceinline__ Slot slot_of(uint8_t* out, long long slot_bytes, long long f) {
+  Slot s;
+  s.stream = out + f * slot_bytes + kStreamAt;
+  const uint32_t mis = (uint32_t)((uintptr_t)s.stream & 3);
+  s.words = (uint32_t*)(s.stream - mis);
+  s.shift = 8 * mis;
+  return s;
+}
+
+__device__ __forceinline__ uint32_t unit_bits(const uint4 v, int valid, const uint8_t* __restrict__ lens) {
+  const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+  uint32_t bits = 0;
+#pragma unroll
+  for (int k = 0; k < 16; k++) bits += k < valid ? lens[(d[k >> 2] >> (8 * (k & 3))) & 255] : 0u;
+  return bits;
+}
+
+__global__ __launch_bounds__(1024) void pngw_scan_kernel(long long nimages, long long F, const uint8_t* __restrict__ filt, long long filt_stride,
+                                                         const uint32_t* __restrict__ tab, unsigned long long* __restrict__ offsets, uint8_t* out,
+                                                         long long slot_bytes) {
+  __shared__ uint8_t lens[260];
+  __shared__ uint32_t wave_total[16];
+  __shared__ unsigned long long carry_s;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long long nunits = (F + 15) >> 4;
+  for (long long f = blockIdx.x; f < nimages; f += gridDim.x) {
+    const uint32_t* __restrict__ tb = tab + f * kTabWords;
+    if (tb[kMeta]) continue;  // stored: nothing is packed
+    __syncthreads();
+    if (t < kLit) lens[t] = (uint8_t)(tb[t] >> 16);
+    const Slot sl = slot_of(out, slot_bytes, f);
+    const unsigned long long start = (unsigned long long)sl.shift + tb[kMeta + 1];
+    for (long long wd = t; wd < (long long)((start + 31) >> 5); wd += 1024) sl.words[wd] = 0;
+    if (t == 0) carry_s = start;
+    __syncthreads();
+    const uint4* __restrict__ src = (const uint4*)(filt + f * filt_stride);
+    unsigned long long* __restrict__ off = offsets + f * nunits;
+    for (long long first = 0; first < nunits; first += 1024) {
+      const long long u = first + t;
+      uint32_t bits = 0;
+      if (u < nunits) {
+        const long long rem = F - u * 16;
+        bits = unit_bits(src[u], rem < 16 ? (int)rem : 16, lens);
+      }
+      uint32_t inc = bits;  // inclusive scan inside the wave: at most 1024 * 240
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t other = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += other;
+      }
+      if (lane == 63) wave_total[wave] = inc;
+      __syncthreads();
+      unsigned long long before = carry_s;
+      for (int k = 0; k < wave; k++) before += wave_total[k];
+      const unsigned long long at = before + inc - bits;
+      if (u < nunits) {
+        off[u] = at;
+        for (unsigned long long wd = (at + 31) >> 5; wd < ((at + bits + 31) >> 5); wd++) sl.words[wd] = 0;
+      }
+      __syncthreads();
+      if (t == 1023) carry_s = before + inc;
+      __syncthreads();
+    }
+    if (t == 0) {  // the end-of-block code
+      const unsigned long long at = carry_s;
+      for (unsigned long long wd = (at + 31) >> 5; wd < ((at + lens[256] + 31) >> 5); wd++) sl.words[wd] = 0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- the stream
+
+// Bits least significant first into 32-bit words.  The words are zero where nothing has been written; the first and the last word
+// of a run are shared with its neighbours and OR-ed in with integer atomics, the words in between are the run's own.
+struct BitPacker {
+  uint32_t* __restrict__ word;
+  unsigned long long acc = 0;
+  int n;
+  bool first = true;
+  __device__ __forceinline__ BitPacker(uint32_t* words, unsigned long long bit) : word(words + (bit >> 5)), n((int)(bit & 31)) {}
+  __device__ __forceinline__ void operator()(uint32_t code) {  // bits | count << 16, count <= 15
+    acc |= (unsigned long long)(code & 0xffffu) << n;
+    n += (int)(code >> 16);
+    if (n >= 32) {
+      if (first) atomicOr(word, (uint32_t)acc);
+      else *word = (uint32_t)acc;
+      first = false;
+      word++;
+      acc >>= 32;
+      n -= 32;
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    if (n > 0 && (uint32_t)acc) atomicOr(word, (uint32_t)acc);
+  }
+};
+
+__global__ __launch_bounds__(256) void pngw_pack_kernel(long long nimages, long long F, int parts, const uint8_t* __restrict__ filt, long long filt_stride,
+                                                        const uint32_t* __restrict__ tab, const unsigned long long* __restrict__ offsets, uint8_t* out,
+                                                        long long slot_bytes) {
+  __shared__ uint32_t codes[kLit];
+  const int t = threadIdx.x;
+  const long long nunits = (F + 15) >> 4;
+  const long long items = nimages * parts;
+  for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+    const long long f = item / parts;
+    const int p = (int)(item - f * parts);
+    const uint32_t* __restrict__ tb = tab + f * kTabWords;
+    const uint8_t* __restrict__ src = filt + f * filt_stride;
+    const Slot sl = slot_of(out, slot_bytes, f);
+    if (tb[kMeta]) {  // stored blocks: byte idx of the stream is header byte r < 5 or data byte r - 5 of block idx / 65540
+      const long long total = stored_bytes(F);
+      const int last = (int)((F - 1) / 65535);
+      for (long long idx = (long long)p * 256 + t; idx < total; idx += (long long)parts * 256) {
+        const int b = (int)(idx / 65540), r = (int)(idx - (long long)b * 65540);
+        uint8_t v;
+        if (r >= 5) {
+          v = src[(long long)b * 65535 + (r - 5)];
+        } else {
+          const long long left = F - (long long)b * 65535;
+          const uint32_t len = left < 65535 ? (uint32_t)left : 65535u;
+          v = r == 0 ? (uint8_t)(b == last) : r == 1 ? (uint8_t)len : r == 2 ? (uint8_t)(len >> 8) : r == 3 ? (uint8_t)~len : (uint8_t)(~len >> 8);
+        }
+        sl.stream[idx] = v;
+      }
+      continue;
+    }
+    __syncthreads();
+    for (int i = t; i < kLit; i += 256) codes[i] = tb[i];
+    __syncthreads();
+    if (p == 0) {
+      const uint32_t hdr_bits = tb[kMeta + 1];
+      for (uint32_t j = t; j < ((hdr_bits + 31) >> 5); j += 256) {
+        const uint32_t v = tb[260 + j];
+        if (v << sl.shift) atomicOr(sl.words + j, v << sl.shift);
+        if (sl.shift && (v >> (32 - sl.shift))) atomicOr(sl.words + j + 1, v >> (32 - sl.shift));
+      }
+      if (t == 0) {
+        const unsigned long long data = (unsigned long long)tb[kMeta + 3] | ((unsigned long long)tb[kMeta + 4] << 32);
+        BitPacker bp(sl.words, (unsigned long long)sl.shift + hdr_bits + data);
+        bp(codes[256]);
+        bp.finish();
+      }
+    }
+    const uint4* __restrict__ src16 = (const uint4*)src;
+    const unsigned long long* __restrict__ off = offsets + f * nunits;
+    for (long long u = (long long)p * 256 + t; u < nunits; u += (long long)parts * 256) {
+      const uint4 v = src16[u];
+      const long long rem = F - u * 16;
+      const int valid = rem < 16 ? (int)rem : 16;
+      const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+      BitPacker bp(sl.words, off[u]);
+#pragma unroll
+      for (int k = 0; k < 16; k++)
+        if (k < valid) bp(codes[(d[k >> 2] >> (8 * (k & 3))) & 255]);
+      bp.finish();
+    }
+  }
+}
+
+// head: 33 bytes (signature, IHDR with its CRC) and the 12 of IEND
+__global__ __launch_bounds__(256) void pngw_finish_kernel(long long nimages, long long F, const uint8_t* __restrict__ head, const uint32_t* __restrict__ zeroed,
+                                                          const uint32_t* __restrict__ tab, uint8_t* out, long long slot_bytes, int32_t* __restrict__ sizes,
+                                                          int32_t* __restrict__ crc_len) {
+  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nimages; f += (long long)gridDim.x * 256) {
+    uint8_t* __restrict__ o = out + f * slot_bytes;
+    const uint32_t stream = tab[f * kTabWords + kMeta + 2];
+    const uint32_t idat = 2 + stream + 4;
+    for (int i = 0; i < 33; i++) o[i] = head[i];
+    for (int i = 0; i < 4; i++) o[33 + i] = (uint8_t)(idat >> (24 - 8 * i));
+    o[37] = 'I', o[38] = 'D', o[39] = 'A', o[40] = 'T', o[41] = 0x78, o[42] = 0x01;
+    const unsigned long long* __restrict__ sums = (const unsigned long long*)(zeroed + f * kZeroWords + kMaxSym);
+    const uint32_t s1 = (uint32_t)((1 + sums[0]) % kAdlerMod), s2 = (uint32_t)(((unsigned long long)F + sums[1]) % kAdlerMod);
+    const uint32_t adler = (s2 << 16) | s1;
+    uint8_t* __restrict__ e = o + kStreamAt + stream;
+    for (int i = 0; i < 4; i++) e[i] = (uint8_t)(adler >> (24 - 8 * i));
+    for (int i = 0; i < 12; i++) e[8 + i] = head[33 + i];
+    sizes[f] = (int32_t)(57 + 6 + stream);
+    crc_len[f] = (int32_t)(4 + idat);
+  }
+}
+
+__global__ __launch_bounds__(256) void pngw_crc_kernel(long long nimages, const uint32_t* __restrict__ tab, const uint32_t* __restrict__ crc, uint8_t* out,
+                                                       long long slot_bytes) {
+  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nimages; f += (long long)gridDim.x * 256) {
+    uint8_t* __restrict__ e = out + f * slot_bytes + kStreamAt + tab[f * kTabWords + kMeta + 2] + 4;
+    const uint32_t c = crc[f];
+    for (int i = 0; i < 4; i++) e[i] = (uint8_t)(c >> (24 - 8 * i));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+
+thread_local char g_error[256] = "";
+
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_error, sizeof g_error, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (dev < 0) return;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) (void)hipSetDevice(dev);
+    else prev = -1;
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+uint32_t crc32_host(const uint8_t* p, size_t n) {
+  uint32_t c = 0xFFFFFFFFu;
+  for (size_t i = 0; i < n; i++) {
+    c ^= p[i];
+    for (int b = 0; b < 8; b++) c = (c >> 1) ^ ((c & 1) ? 0xEDB88320u : 0u);
+  }
+  return ~c;
+}
+
+void put_be32(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
+}
+
+int grid_for(long long items) { return (int)(items < 1 ? 1 : items > kMaxGrid ? kMaxGrid : items); }
+
+}  // namespace
+
+struct mdcp_encoder {
+  int device = -1, w = 0, h = 0, depth = 0, filter = 0, max_images = 0;
+  long long F = 0, nunits = 0;
+  uint8_t* d_head = nullptr;
+  uint8_t* d_filt = nullptr;
+  unsigned long long* d_offsets = nullptr;
+  uint32_t* d_zeroed = nullptr;
+  uint32_t* d_tab = nullptr;
+  int32_t* d_crc_len = nullptr;
+  uint32_t* d_crc = nullptr;
+  uint8_t* d_out = nullptr;  // mdcp_output_device: allocated on demand
+  int32_t* d_sizes = nullptr;
+};
+
+extern "C" {
+
+int64_t mdcp_png_bound(int w, int h, int depth) {
+  if (w < 1 || h < 1 || (depth != 8 && depth != 16)) return -1;
+  const int64_t row = 1 + (int64_t)w * (depth / 8);  // < 2^33
+  if (row > INT32_MAX / (int64_t)h) return -1;
+  const int64_t bound = 57 + 6 + stored_bytes(row * h);
+  return bound > INT32_MAX ? -1 : bound;
+}
+
+const char* mdcp_last_error(void) { return g_error; }
+
+void mdcp_destroy(mdcp_encoder* enc) {
+  if (!enc) return;
+  {
+    DeviceGuard dg(enc->device);
+    (void)hipFree(enc->d_head);
+    (void)hipFree(enc->d_filt);
+    (void)hipFree(enc->d_offsets);
+    (void)hipFree(enc->d_zeroed);
+    (void)hipFree(enc->d_tab);
+    (void)hipFree(enc->d_crc_len);
+    (void)hipFree(enc->d_crc);
+    (void)hipFree(enc->d_out);
+    (void)hipFree(enc->d_sizes);
+  }
+  delete enc;
+}
+
+int mdcp_create(int device, int w, int h, int depth, int filter, int max_images, mdcp_encoder** out) {
+  if (!out) return fail(MDCP_ERR_ARG, "mdcp_create: out is null");
+  *out = nullptr;
+  if (depth != 8 && depth != 16) return fail(MDCP_ERR_ARG, "mdcp_create: depth %d is neither 8 nor 16", depth);
+  if (filter < 0 || filter > MDCP_FILTER_ADAPTIVE) return fail(MDCP_ERR_ARG, "mdcp_create: filter %d is outside 0..%d", filter, MDCP_FILTER_ADAPTIVE);
+  if (max_images < 1) return fail(MDCP_ERR_ARG, "mdcp_create: max_images %d is below 1", max_images);
+  if (w < 1 || h < 1) return fail(MDCP_ERR_SIZE, "mdcp_create: %d x %d: width and height start at 1", w, h);
+  if (mdcp_png_bound(w, h, depth) < 0) return fail(MDCP_ERR_SIZE, "mdcp_create: a %d x %d image of %d bits passes 2^31 - 1 bytes (sizes are int32_t)", w, h, depth);
+  const long long F = (1 + (long long)w * (depth / 8)) * h, nunits = (F + 15) / 16;
+  const long long per_image = 24 * nunits + kSmallBytes;
+  if (per_image > (1ll << 40) / max_images)
+    return fail(MDCP_ERR_SIZE, "mdcp_create: %d images x %lld bytes of scratch pass 2^40 bytes", max_images, per_image);
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MDCP_ERR_NO_DEVICE, "mdcp_create: no HIP device");
+  if (device >= count) return fail(MDCP_ERR_NO_DEVICE, "mdcp_create: device %d of %d", device, count);
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(MDCP_ERR_HIP, "mdcp_create: hipGetDevice failed");
+  DeviceGuard dg(device);
+  mdcp_encoder* e = new (std::nothrow) mdcp_encoder;
+  if (!e) return fail(MDCP_ERR_NOMEM, "mdcp_create: out of host memory");
+  e->device = device, e->w = w, e->h = h, e->depth = depth, e->filter = filter, e->max_images = max_images;
+  e->F = F, e->nunits = nunits;
+  const size_t n = (size_t)max_images;
+  if (hipMalloc((void**)&e->d_head, 48) != hipSuccess || hipMalloc((void**)&e->d_filt, n * (size_t)nunits * 16) != hipSuccess ||
+      hipMalloc((void**)&e->d_offsets, n * (size_t)nunits * 8) != hipSuccess || hipMalloc((void**)&e->d_zeroed, n * kZeroWords * 4) != hipSuccess ||
+      hipMalloc((void**)&e->d_tab, n * kTabWords * 4) != hipSuccess || hipMalloc((void**)&e->d_crc_len, n * 4) != hipSuccess ||
+      hipMalloc((void**)&e->d_crc, n * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    mdcp_destroy(e);
+    return fail(MDCP_ERR_NOMEM, "mdcp_create: could not allocate the scratch arrays of %d images of %d x %d", max_images, w, h);
+  }
+  uint8_t head[48] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n', 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
+  put_be32(head + 16, (uint32_t)w);
+  put_be32(head + 20, (uint32_t)h);
+  head[24] = (uint8_t)depth;  // colour type, compression, filter method, interlace: 0
+  put_be32(head + 29, crc32_host(head + 12, 17));
+  const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
+  memcpy(head + 33, iend, 12);
+  if (hipMemcpy(e->d_head, head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) {
+    mdcp_destroy(e);
+    return fail(MDCP_ERR_HIP, "mdcp_create: copying the header failed");
+  }
+  *out = e;
+  return MDCP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+template <typename T, int BPP>
+int encode(const char* who, mdcp_encoder* e, const T* d_images, int64_t stride, int nimages, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes, void* stream) {
+  if (!e) return fail(MDCP_ERR_ARG, "%s: encoder is null", who);
+  if (e->depth != 8 * BPP) return fail(MDCP_ERR_ARG, "%s: the encoder was made for %d-bit images", who, e->depth);
+  if (nimages < 0 || nimages > e->max_images) return fail(MDCP_ERR_ARG, "%s: %d images, the encoder was made for 0..%d", who, nimages, e->max_images);
+  if (nimages == 0) return MDCP_OK;
+  if (!d_images || !d_out || !d_sizes) return fail(MDCP_ERR_ARG, "%s: null device pointer", who);
+  if ((uintptr_t)d_images % sizeof(T)) return fail(MDCP_ERR_ARG, "%s: d_images %p is not aligned to its %zu-byte elements", who, (const void*)d_images, sizeof(T));
+  if (stride < (int64_t)e->w * e->h) return fail(MDCP_ERR_ARG, "%s: stride %lld is below %d x %d", who, (long long)stride, e->w, e->h);
+  const int64_t bound = mdcp_png_bound(e->w, e->h, e->depth);
+  if (slot_bytes < bound)
+    return fail(MDCP_ERR_SIZE, "%s: slot_bytes %lld is below mdcp_png_bound(%d, %d, %d) = %lld", who, (long long)slot_bytes, e->w, e->h, e->depth, (long long)bound);
+  DeviceGuard dg(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  const long long n = nimages, F = e->F, fs = e->nunits * 16;
+  if (hipMemsetAsync(e->d_zeroed, 0, (size_t)n * kZeroWords * 4, s) != hipSuccess)
+    return fail(MDCP_ERR_HIP, "%s: clearing the histograms failed: %s", who, hipGetErrorString(hipGetLastError()));
+  const long long groups = ((long long)e->h + kRowsPerGroup - 1) / kRowsPerGroup;
+  long long parts = (e->nunits + 1023) / 1024;
+  if (n * parts < 1024) parts = (1024 + n - 1) / n;  // few images: still fill the device
+  if (parts > (e->nunits + 255) / 256) parts = (e->nunits + 255) / 256;
+  if (parts > 4096) parts = 4096;
+  pngw_filter_kernel<T, BPP><<<grid_for(n * groups), 256, 0, s>>>(d_images, (long long)stride, n, e->w, e->h, e->filter, e->d_filt, fs, e->d_zeroed);
+  pngw_build_kernel<<<grid_for(n), 256, 0, s>>>(n, F, e->d_zeroed, e->d_tab);
+  pngw_scan_kernel<<<grid_for(n), 1024, 0, s>>>(n, F, e->d_filt, fs, e->d_tab, e->d_offsets, d_out, (long long)slot_bytes);
+  pngw_pack_kernel<<<grid_for(n * parts), 256, 0, s>>>(n, F, (int)parts, e->d_filt, fs, e->d_tab, e->d_offsets, d_out, (long long)slot_bytes);
+  pngw_finish_kernel<<<grid_for((n + 255) / 256), 256, 0, s>>>(n, F, e->d_head, e->d_zeroed, e->d_tab, d_out, (long long)slot_bytes, d_sizes, e->d_crc_len);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(MDCP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
+  if (mdcz_crc32_device(d_out + 37, slot_bytes, e->d_crc_len, n, e->d_crc, stream) != MDCZ_OK)
+    return fail(MDCP_ERR_HIP, "%s: the IDAT checksum failed: %s", who, mdcz_last_error());
+  pngw_crc_kernel<<<grid_for((n + 255) / 256), 256, 0, s>>>(n, e->d_tab, e->d_crc, d_out, (long long)slot_bytes);
+  if ((err = hipGetLastError()) != hipSuccess) return fail(MDCP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
+  return MDCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdcp_encode_u8_device(mdcp_encoder* enc, const uint8_t* d_images, int64_t stride, int nimages, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes,
+                          void* stream) {
+  return encode<uint8_t, 1>("mdcp_encode_u8_device", enc, d_images, stride, nimages, d_out, slot_bytes, d_sizes, stream);
+}
+
+int mdcp_encode_u16_device(mdcp_encoder* enc, const uint16_t* d_images, int64_t stride, int nimages, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes,
+                           void* stream) {
+  return encode<uint16_t, 2>("mdcp_encode_u16_device", enc, d_images, stride, nimages, d_out, slot_bytes, d_sizes, stream);
+}
+
+int mdcp_encode_f32_device(mdcp_encoder* enc, const float* d_images, int64_t stride, int nimages, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes,
+                           void* stream) {
+  return encode<float, 1>("mdcp_encode_f32_device", enc, d_images, stride, nimages, d_out, slot_bytes, d_sizes, stream);
+}
+
+int mdcp_output_device(mdcp_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
+  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(MDCP_ERR_ARG, "mdcp_output_device: null argument");
+  const int64_t bound = mdcp_png_bound(enc->w, enc->h, enc->depth);
+  if (!enc->d_out) {
+    DeviceGuard dg(enc->device);
+    uint8_t* o = nullptr;
+    int32_t* z = nullptr;
+    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_images) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_images * sizeof(int32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(o);
+      return fail(MDCP_ERR_NOMEM, "mdcp_output_device: could not allocate %d slots of %lld bytes", enc->max_images, (long long)bound);
+    }
+    enc->d_out = o, enc->d_sizes = z;
+  }
+  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
+  return MDCP_OK;
+}
+
+int mdcp_huffman_lengths_device(const uint32_t* d_hist, int nsym, int limit, uint8_t* d_lengths, void* stream) {
+  const char* who = "mdcp_huffman_lengths_device";
+  if (!d_hist || !d_lengths) return fail(MDCP_ERR_ARG, "%s: null pointer", who);
+  if (nsym < 1 || nsym > kMaxSym) return fail(MDCP_ERR_ARG, "%s: nsym %d is outside 1..%d", who, nsym, kMaxSym);
+  if (limit < 1 || limit > 15) return fail(MDCP_ERR_ARG, "%s: limit %d is outside 1..15", who, limit);
+  if (nsym > (1 << limit)) return fail(MDCP_ERR_ARG, "%s: %d symbols do not fit codes of at most %d bits", who, nsym, limit);
+  pngw_lengths_kernel<<<1, 256, 0, (hipStream_t)stream>>>(d_hist, nsym, limit, d_lengths);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(MDCP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
+  return MDCP_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,5 @@
-// rectifyDataset <dataset folder> <output folder> [quality=95]: a sequence, rectified, as a dataset of its own.
+// rectifyDataset <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1]: a sequence, rectified, as a dataset
+// of its own.  The key=value arguments may stand in any position behind the two folders; a bare number is the JPEG quality.
 // The frames are those of playDataset's saving mode -- getImage(i, true, false, false, false), encoded by include/mdc_jenc.h with the
 // bytes cv::imwrite gives a CV_32F image -- but they go into one images.zip of stored %05d.jpg entries, built on the device by
 // include/mdc_zipw.h, and the folder gets what a reader needs to open it:
@@ -7,14 +8,24 @@
 //                "w h" -- with omega = 0 a reader takes the relative intrinsics as they are (the reference's src/FOVUndistorter.cpp:144-150)
 //   times.txt    the source's lines, verbatim, of the frames that were written (only if the source has the file)
 //   pcalib.txt   copied verbatim (if present)
-// vignette.png is NOT exported: a rectified vignette needs a 16-bit PNG writer and a decision about the black border pixels, so the
-// exported dataset opens with validVignette == false, as any dataset without that file does.
+// frames=png: images.zip holds %05d.png entries instead, 8-bit, lossless: the same rectified float frames converted as the JPEG
+// encoder converts them (rintf, clamped to 0..255, NaN -> 0) and encoded on the device by include/mdc_pngw.h; no JPEG encoder is made.
+// vignette.png is NOT exported by default, and the exported dataset then opens with validVignette == false, as any dataset without
+// that file does.  vignette=1 writes <out>/vignette.png, 16-bit, if the source has a valid vignette (one line says so if not):
+//   V = the source's vignetteMap (normalised to a maximum of 1; not the inverse);  R = undistort<float>(V) through the sequence's
+//   own UndistorterFOV, on the device like any frame;  m = the maximum of the finite positive R;  every pixel is
+//   clamp(rintf(R / m * 65535), 1, 65535), and every pixel whose R is not a finite positive number -- the black border the remap
+//   marks with -1, a tap on a zero of the source map -- is 65535.
+//   A reader normalises by the maximum and inverts, so the exported map never yields inf or NaN, and a black border pixel, 0 in
+//   every frame, stays 0.  GInv[rect(I)] * Vinv_rect approximates rect(GInv[I] * Vinv); it is exact only where the vignette is
+//   locally constant.  The quantisation is a one-time table step on the host; the PNG is encoded by mdcp_encode_u16_device.
 // The output folder is created if missing; files of these names are overwritten, nothing is deleted.  A frame the reader cannot
 // deliver is reported and left out (of images.zip and of times.txt).
 #include <sys/stat.h>
 #include <sys/types.h>
 
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,7 +35,9 @@
 
 #include "BenchmarkDatasetReader.h"
 #include "mdc_hip.h"
+#include "mdc_host.h"
 #include "mdc_jenc.h"
+#include "mdc_pngw.h"
 #include "mdc_zipw.h"
 
 static bool make_dirs(const std::string& path) {
@@ -59,13 +72,84 @@ static std::vector<std::string> time_lines(const std::string& file, bool* presen
   return lines;
 }
 
+// The rectified vignette as <out>/vignette.png (the rule is in the header comment).  Returns 0, also when the source has none.
+static int export_vignette(DatasetReader* reader, const std::string& dataset, const std::string& out, int w, int h) {
+  mdc_ctx* ctx = reader->getContext();
+  const Eigen::Vector2i in = reader->getUndistorter()->getInputDims();
+  const size_t n_in = (size_t)in[0] * in[1], n_out = (size_t)w * h;
+  mdch_photo* photo = mdch_photo_create((dataset + "pcalib.txt").c_str(), (dataset + "vignette.png").c_str(), in[0], in[1]);
+  std::vector<float> map(n_in), rect(n_out, 0.0f);
+  const bool valid = photo && (mdch_photo_valid(photo) & 2) && mdch_photo_vignette(photo, map.data(), 0);
+  if (photo) mdch_photo_destroy(photo);
+  if (!valid) {
+    printf("vignette.png: the source has no valid vignette: nothing written\n");
+    return 0;
+  }
+  reader->getUndistorter()->undistort<float>(map.data(), rect.data(), (int)n_in, (int)n_out);
+  float top = 0.0f;
+  for (size_t i = 0; i < n_out; i++)
+    if (std::isfinite(rect[i]) && rect[i] > top) top = rect[i];
+  std::vector<uint16_t> q(n_out);
+  size_t border = 0;
+  for (size_t i = 0; i < n_out; i++) {
+    const float r = rect[i];
+    if (std::isfinite(r) && r > 0.0f) {
+      const float v = rintf(r / top * 65535.0f);
+      q[i] = (uint16_t)(v < 1.0f ? 1.0f : v > 65535.0f ? 65535.0f : v);
+    } else {
+      q[i] = 65535, border++;
+    }
+  }
+  mdcp_encoder* enc = 0;
+  uint16_t* d_q = 0;
+  uint8_t* d_png = 0;
+  int32_t* d_size = 0;
+  int64_t slot = 0;
+  int32_t size = 0;
+  int status = 1;
+  std::vector<uint8_t> file;
+  if (mdcp_create(reader->getDevice(), w, h, 16, MDCP_FILTER_ADAPTIVE, 1, &enc) != MDCP_OK || mdcp_output_device(enc, &d_png, &slot, &d_size) != MDCP_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
+  } else if (mdc_device_alloc(ctx, n_out * sizeof(uint16_t), (void**)&d_q) != MDC_OK || mdc_copy_to_device(ctx, d_q, q.data(), n_out * sizeof(uint16_t)) != MDC_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdc_last_error(ctx));
+  } else if (mdcp_encode_u16_device(enc, d_q, (int64_t)n_out, 1, d_png, slot, d_size, 0) != MDCP_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
+  } else if (mdc_copy_to_host(ctx, &size, d_size, sizeof size) != MDC_OK || size <= 0 || size > slot ||
+             (file.resize((size_t)size), mdc_copy_to_host(ctx, file.data(), d_png, (size_t)size)) != MDC_OK) {
+    fprintf(stderr, "rectifyDataset: reading vignette.png back failed: %s\n", mdc_last_error(ctx));
+  } else {
+    FILE* f = fopen((out + "/vignette.png").c_str(), "wb");
+    const bool ok = f && fwrite(file.data(), 1, file.size(), f) == file.size();
+    if ((f && fclose(f) != 0) || !ok) fprintf(stderr, "rectifyDataset: cannot write %s/vignette.png\n", out.c_str());
+    else status = 0;
+  }
+  if (d_q) mdc_device_free(ctx, d_q);
+  mdcp_destroy(enc);
+  if (!status) printf("vignette.png: %d x %d, 16-bit, %d bytes, %zu border pixels at 65535\n", w, h, (int)size, border);
+  return status;
+}
+
 int main(int argc, char** argv) {
+  const char* usage = "usage: %s <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1]\n";
   if (argc < 3) {
-    fprintf(stderr, "usage: %s <dataset folder> <output folder> [quality=95]\n", argv[0]);
+    fprintf(stderr, usage, argv[0]);
     return 1;
   }
   std::string dataset = argv[1], out = argv[2];
-  const int quality = argc > 3 ? atoi(argv[3]) : 95;
+  int quality = 95;
+  bool png = false, vignette = false;
+  for (int i = 3; i < argc; i++) {
+    const std::string a = argv[i];
+    if (a == "frames=png" || a == "frames=jpg") png = a == "frames=png";
+    else if (a == "vignette=1" || a == "vignette=0") vignette = a == "vignette=1";
+    else if (a.compare(0, 8, "quality=") == 0) quality = atoi(a.c_str() + 8);
+    else if (a.find('=') == std::string::npos) quality = atoi(argv[i]);
+    else {
+      fprintf(stderr, "rectifyDataset: unknown argument %s\n", argv[i]);
+      fprintf(stderr, usage, argv[0]);
+      return 1;
+    }
+  }
   if (dataset.empty() || dataset[dataset.size() - 1] != '/') dataset += "/";  // the reader wants the trailing slash
   while (out.size() > 1 && out[out.size() - 1] == '/') out.erase(out.size() - 1);
   if (out.empty() || !make_dirs(out)) {
@@ -82,12 +166,18 @@ int main(int argc, char** argv) {
     delete reader;
     return 1;
   }
-  printf("Rectifying %s: %d frames of %d x %d into %s (JPEG quality %d)\n", dataset.c_str(), total, w, h, out.c_str(), quality);
+  if (png) printf("Rectifying %s: %d frames of %d x %d into %s (PNG, 8-bit, lossless)\n", dataset.c_str(), total, w, h, out.c_str());
+  else printf("Rectifying %s: %d frames of %d x %d into %s (JPEG quality %d)\n", dataset.c_str(), total, w, h, out.c_str(), quality);
 
   const int chunk = total < 128 ? (total > 0 ? total : 1) : 128;
   const size_t frame = (size_t)w * h;
   mdcj_encoder* enc = 0;
-  if (mdcj_create(reader->getDevice(), w, h, quality, chunk, &enc) != MDCJ_OK) {
+  mdcp_encoder* penc = 0;
+  if (png && mdcp_create(reader->getDevice(), w, h, 8, MDCP_FILTER_ADAPTIVE, chunk, &penc) != MDCP_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
+    return 1;
+  }
+  if (!png && mdcj_create(reader->getDevice(), w, h, quality, chunk, &enc) != MDCJ_OK) {
     fprintf(stderr, "rectifyDataset: %s\n", mdcj_last_error());
     return 1;
   }
@@ -99,8 +189,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "rectifyDataset: %s\n", mdc_last_error(ctx));
     return 1;
   }
-  if (mdcj_output_device(enc, &d_out, &slot, &d_sizes) != MDCJ_OK) {
-    fprintf(stderr, "rectifyDataset: %s\n", mdcj_last_error());
+  if (png ? mdcp_output_device(penc, &d_out, &slot, &d_sizes) != MDCP_OK : mdcj_output_device(enc, &d_out, &slot, &d_sizes) != MDCJ_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", png ? mdcp_last_error() : mdcj_last_error());
     return 1;
   }
   mdcz_writer* zip = 0;
@@ -123,12 +213,13 @@ int main(int argc, char** argv) {
       break;
     }
     // positions without a frame are encoded too (whatever they hold is a legal input) and left out of the archive
-    if (mdcj_encode_f32_device(enc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJ_OK) {
-      fprintf(stderr, "rectifyDataset: %s\n", mdcj_last_error());
+    if (png ? mdcp_encode_f32_device(penc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCP_OK
+            : mdcj_encode_f32_device(enc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJ_OK) {
+      fprintf(stderr, "rectifyDataset: %s\n", png ? mdcp_last_error() : mdcj_last_error());
       status = 1;
       break;
     }
-    if (mdcz_append_device(zip, d_out, slot, d_sizes, valid.data(), n, first, ".jpg", 0) != MDCZ_OK) {
+    if (mdcz_append_device(zip, d_out, slot, d_sizes, valid.data(), n, first, png ? ".png" : ".jpg", 0) != MDCZ_OK) {
       fprintf(stderr, "rectifyDataset: %s\n", mdcz_last_error());
       status = 1;
       break;
@@ -140,6 +231,7 @@ int main(int argc, char** argv) {
   }
   mdc_device_free(ctx, d_frames);
   mdcj_destroy(enc);
+  mdcp_destroy(penc);
   if (status) {
     mdcz_abort(zip);
     delete reader;
@@ -183,7 +275,8 @@ int main(int argc, char** argv) {
       status = 1;
     }
   }
-  printf("vignette.png is not exported (a rectified vignette is out of scope): the dataset opens without a vignette.\n");
+  if (!vignette) printf("vignette.png is not exported (a rectified vignette is out of scope): the dataset opens without a vignette.\n");
+  else if (export_vignette(reader, dataset, out, w, h) != 0) status = 1;
   delete reader;
   return status;
 }
