@@ -85,6 +85,8 @@ MDC_API void mdch_reader_raw_dims(mdch_reader*, int wh[2]); /* getRawSize() */
 MDC_API void mdch_reader_set_threads(mdch_reader*, int n);       /* setDecodeThreads() */
 MDC_API void mdch_reader_set_prefetch(mdch_reader*, int frames); /* setPrefetch() */
 MDC_API void mdch_reader_set_lookahead(mdch_reader*, int frames); /* setResultLookahead(): getImage results made ahead on JPEG sequences read in order */
+MDC_API void mdch_reader_set_gpu_png(mdch_reader*, int mode);     /* setGpuPngMode(): 0 host, 1 the stream classes that win on the device, 2 every eligible stream */
+MDC_API long mdch_reader_png_device_frames(mdch_reader*);         /* frames libmdc_pngd.so decoded for getImagesDevice over the reader's life */
 MDC_API void mdch_reader_set_gpu_jpeg(mdch_reader*, int stage);   /* setGpuJpegStage(): 0 host, 1 device inverse DCT, 2 (or any other) device Huffman too */
 MDC_API const char* mdch_reader_last_error(mdch_reader*);
 MDC_API void mdch_reader_prefetch_stats(mdch_reader*, long hits_misses[2]); /* getPrefetchStats() */
@@ -111,6 +113,12 @@ MDC_API int mdch_decode_jpeg_record(const unsigned char* data, size_t n, void* r
  * Returns the bytes written, 0 (reason in err) for what the device decoder does not take -- more than one component,
  * progressive files, restart markers, a stream that does not fit: decode those with mdch_decode_jpeg_record / _gray8. */
 MDC_API long long mdch_jpeg_stream(const unsigned char* data, size_t n, void* stream, size_t cap, int wh[2], char* err, size_t errcap);
+
+/* The host part of PNG decoding when the GPU inflates and unfilters (mdci_decode_host, include/mdc_pngd.h): walks the chunks of an
+ * 8-bit grayscale, non-interlaced file and copies its IDAT bodies, concatenated -- the zlib stream -- to dst (cap bytes).  1 with
+ * *w, *h, *stream_bytes set; 0 for every other flavour (16-bit, palette, colour, alpha, interlaced), a file without IHDR, a truncated
+ * chunk or a stream longer than cap: decode those with mdch_decode_gray8. */
+MDC_API int mdch_png_stream(const unsigned char* file, size_t bytes, int* w, int* h, unsigned char* dst, size_t cap, size_t* stream_bytes);
 
 /* ExposureImage's pixel pool (include/mono_dataset_code/ExposureImage.h): page-locked blocks carved out of slabs of up to 64
  * images, lowest free address first (consecutive images lie back to back: a chunk of results leaves the GPU with one copy).  mdch_image_pool_trim releases every slab without a live image; mdch_image_pool_idle_bytes = the bytes it would release. */

@@ -105,6 +105,15 @@ class MDC_API DatasetReader {
   // on the host.  Same bytes in every stage.  setGpuJpeg(on) = stage 2 / 0; MDC_GPU_JPEG=0|1|2 in the environment.
   void setGpuJpeg(bool on);
   void setGpuJpegStage(int stage);
+  // getImagesDevice on PNG sequences (8-bit grayscale, non-interlaced): the decode threads only walk the chunks, libmdc_pngd.so (loaded
+  // at first use from the directory of this library, or MDC_LIB_PNGD) inflates, checks and unfilters on the GPU and the fused pass reads
+  // the pixels where they are.  Mode 1 (default): the stream classes measured faster than the host decoder (a single
+  // final Huffman-only block, what bin/rectifyDataset frames=png writes); 2: every eligible stream;
+  // 0: the host decoder.  A stream the device refuses goes to the host decoder.  Same bytes in every mode.  setGpuPng(on) = 1 / 0;
+  // MDC_GPU_PNG=0|1|2 in the environment.  getImages, getImage and getImagesRawDevice decode PNG on the host.
+  void setGpuPng(bool on);
+  void setGpuPngMode(int mode);
+  long pngDeviceFrames() const;  // frames the device decoder produced so far
   // getImage on a JPEG sequence read in order (stage 2): from the third consecutive id on, the next results are made ahead in
   // one pass of the getImages pipeline with the caller's switches and handed out by the following calls: 64, then 128, then
   // 256 at a time while the caller keeps reading in order, never more than `frames` (default 256, 0 = off, also

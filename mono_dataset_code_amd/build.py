@@ -32,7 +32,7 @@ HOST_SOURCES = [os.path.join(HOST, f) for f in (
 HOST_DEPS = HOST_SOURCES + [os.path.join(HOST, "mdc_host_exports.map"), os.path.join(HOST, "gray_png.h"), os.path.join(HOST, "host_device.h"),
                             os.path.join(HOST, "image_codecs.h"), os.path.join(HOST, "image_codecs_internal.h"), os.path.join(HOST, "image_codecs_jpeg.h"), os.path.join(HOST, "zip_reader.h"),
                             os.path.join(HOST, "frame_source.h"), os.path.join(HOST, "decode_pool.h"), os.path.join(HOST, "prefetch_cache.h"),
-                            os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"),
+                            os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"), os.path.join(CSRC, "png_inflate_core.h"),
                             os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h"),
                             os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_host.h"),
                             os.path.join(INC, "mono_dataset_code", "FOVUndistorter.h"),
@@ -284,6 +284,30 @@ def build_pngw(force=False):
     return LIB_PNGW
 
 
+LIB_PNGD = os.path.join(PKG, "libmdc_pngd.so")
+PNGD_SOURCE = os.path.join(CSRC, "mdc_pngd.hip")
+PNGD_CORE = os.path.join(CSRC, "png_inflate_core.h")
+PNGD_EXPORT_MAP = os.path.join(CSRC, "mdc_pngd_exports.map")
+
+
+def build_pngd(force=False):
+    """libmdc_pngd.so: the device PNG decoder (include/mdc_pngd.h) -- one translation unit plus the core header it shares with the CPU
+    test program, independent of every other library here and outside libmdc_hip.so's build identity.  The dataset reader loads it
+    at run time (csrc/host/device_lanes.cpp), nothing links it."""
+    if force or _stale(LIB_PNGD, [PNGD_SOURCE, PNGD_CORE, os.path.join(INC, "mdc_pngd.h"), PNGD_EXPORT_MAP]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, PNGD_SOURCE, "-Wl,--version-script=" + PNGD_EXPORT_MAP, "-o", LIB_PNGD])
+    return LIB_PNGD
+
+
+def build_pngd_core_program(out, sanitize=True):
+    """tests/native/pngd_core.cpp: png_inflate_core.h as a stand-alone program (its own main), under AddressSanitizer and
+    UndefinedBehaviorSanitizer (tests/test_pngd_cpu.py).  Pure host code: no HIP, no library of ours."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pngd_core.cpp"), "-o", out])
+    return out
+
+
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")
 MULTI_SOURCE = os.path.join(CSRC, "mdc_multi.hip")
 
@@ -356,6 +380,7 @@ def build_all(force=False):
     build_jenc(force)
     build_zipw(force)
     build_pngw(force)
+    build_pngd(force)
     build_debug()
     build_fault_injection()
     return LIB_HIP, LIB_HOST, LIB_MULTI

@@ -249,6 +249,8 @@ HOST_API = {  # include/mdc_host.h (libmdc_host.so)
     "mdch_reader_set_prefetch": (None, [_vp, _i]),
     "mdch_reader_set_lookahead": (None, [_vp, _i]),
     "mdch_reader_set_gpu_jpeg": (None, [_vp, _i]),
+    "mdch_reader_set_gpu_png": (None, [_vp, _i]),
+    "mdch_reader_png_device_frames": (C.c_long, [_vp]),
     "mdch_reader_last_error": (_cp, [_vp]),
     "mdch_reader_prefetch_stats": (None, [_vp, _vp]),
     "mdch_reader_device_stats": (_i, [_vp, _i, _vp, _vp]),
@@ -257,6 +259,7 @@ HOST_API = {  # include/mdc_host.h (libmdc_host.so)
     "mdch_jpeg_record_bytes": (_sz, [_i, _i, _vp]),
     "mdch_decode_jpeg_record": (_i, [_vp, _sz, _vp, _sz, _i, _vp, _cp, _sz]),
     "mdch_jpeg_stream": (C.c_longlong, [_vp, _sz, _vp, _sz, _vp, _cp, _sz]),
+    "mdch_png_stream": (_i, [_vp, _sz, _P(_i), _P(_i), _vp, _sz, _P(_sz)]),
     # ---- ExposureImage's pixel pool
     "mdch_image_alloc": (_vp, [C.c_ulong]),
     "mdch_image_free": (None, [_vp]),
@@ -305,18 +308,32 @@ PNGW_API = {  # include/mdc_pngw.h (libmdc_pngw.so: the device PNG encoder, a li
     "mdcp_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
     "mdcp_huffman_lengths_device": (_i, [_vp, _i, _i, _vp, _vp]),
 }
+PNGD_API = {  # include/mdc_pngd.h (libmdc_pngd.so: the device PNG decoder, a library of its own)
+    "mdci_last_error": (_cp, []),
+    "mdci_scratch_bytes": (_i64, [_i, _i, _i]),
+    "mdci_create": (_i, [_i, _i, _i, _i, _P(_vp)]),
+    "mdci_destroy": (None, [_vp]),
+    "mdci_decode_device": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "mdci_decode_host": (_i, [_vp, _vp, _vp, _i, _vp, _P(_vp)]),
+    "mdci_profile": (_i, [_vp, _i]),
+    "mdci_kernel_ms": (_i, [_vp, _P(_f)]),
+    "mdci_stream": (_vp, [_vp]),
+    "mdci_synchronize": (_i, [_vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
 LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
 LIB_ZIPW_PATH = os.path.join(_PKG, "libmdc_zipw.so")
 LIB_PNGW_PATH = os.path.join(_PKG, "libmdc_pngw.so")
+LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
 _hip = None
 _host = None
 _bench = None
 _jenc = None
 _zipw = None
 _pngw = None
+_pngd = None
 
 
 def _share_hip_runtime_with_torch():
@@ -388,6 +405,15 @@ def pngw_lib():
         _share_hip_runtime_with_torch()
         _pngw = _load(LIB_PNGW_PATH, PNGW_API)
     return _pngw
+
+
+def pngd_lib():
+    """libmdc_pngd.so: the PNG decoder for frames whose zlib streams are in device or host memory (include/mdc_pngd.h)."""
+    global _pngd
+    if _pngd is None:
+        _share_hip_runtime_with_torch()
+        _pngd = _load(LIB_PNGD_PATH, PNGD_API)
+    return _pngd
 
 
 def hip_lib():
@@ -1154,6 +1180,68 @@ class PngEncoder:
         return d_out, int(slot_bytes), d_sizes
 
 
+PNGD_PATHS = {1: "parallel", 2: "stored", 3: "general"}  # MDCI_PATH_*
+
+
+class PngDecoder:
+    """One mdci_decoder (include/mdc_pngd.h): the zlib streams of w x h 8-bit grayscale PNG frames -> pixels on the device.  A
+    status is reason | path << 16 (reason 0: decoded); status_fields() splits an array of them."""
+
+    def __init__(self, w, h, max_images=1, device=-1):
+        self._L = pngd_lib()
+        self.w, self.h, self.max_images = int(w), int(h), int(max_images)
+        h_ = _vp()
+        self._check(self._L.mdci_create(int(device), self.w, self.h, self.max_images, C.byref(h_)))
+        self._h = h_
+        self.scratch_bytes = int(self._L.mdci_scratch_bytes(self.w, self.h, self.max_images))
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MdcError(int(rc), self._L.mdci_last_error().decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mdci_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def profile(self, on=True):
+        """HIP events around the four kernels of every decode_device call from now on (kernel_ms reads the last call's)"""
+        self._check(self._L.mdci_profile(self._h, int(bool(on))))
+
+    def kernel_ms(self):
+        """-> (front, wave-per-image inflate, checks, unfilter) of the last timed call, in ms; waits for it"""
+        ms = (_f * 4)()
+        self._check(self._L.mdci_kernel_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    @staticmethod
+    def status_fields(status):
+        """-> (reasons, paths) of an array of statuses"""
+        s = np.asarray(status, np.int64)
+        return s & 0xffff, (s >> 16) & 0xff
+
+    def decode_device(self, d_slots, slot_bytes, d_sizes, n, d_frames, d_status, skip_head=0, skip_tail=0, frame_stride=None, stream=0):
+        """device addresses throughout: n slots of slot_bytes, int32 sizes -> frames frame_stride bytes apart (default w * h) and
+        int32 statuses; enqueues on `stream` and does not synchronise"""
+        self._check(self._L.mdci_decode_device(self._h, d_slots, int(slot_bytes), d_sizes, int(skip_head), int(skip_tail), int(n), d_frames,
+                                               self.w * self.h if frame_stride is None else int(frame_stride), d_status, _stream(stream)))
+
+    def decode_host(self, streams):
+        """streams: a list of bytes -> (statuses as an int32 array, the device address of the decoder's dense n x h x w array, valid
+        until the next call); blocking"""
+        n = len(streams)
+        keep = [np.frombuffer(bytes(s), np.uint8) for s in streams]
+        ptrs = (_vp * max(n, 1))(*[k.ctypes.data if k.size else None for k in keep])
+        sizes = np.asarray([k.size for k in keep], np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        d_frames = _vp()
+        self._check(self._L.mdci_decode_host(self._h, ptrs, _np_ptr(sizes) if n else None, n, _np_ptr(status), C.byref(d_frames)))
+        return status[:n], d_frames.value
+
+
 def huffman_lengths_device(d_hist, nsym, limit, d_lengths, stream=None):
     """mdcp_huffman_lengths_device: the encoder's code builder on nsym uint32 counts -> nsym uint8 lengths (device addresses)"""
     L = pngw_lib()
@@ -1292,6 +1380,18 @@ def jpeg_stream(data, stream):
     return int(used), int(wh[0]), int(wh[1])
 
 
+def png_stream(data, cap=None):
+    """The zlib stream (the IDAT bodies, concatenated) of an 8-bit grayscale, non-interlaced PNG file -> (w, h, stream bytes);
+    ValueError for every other file and for a stream longer than `cap` (default: the file's length)."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(max(buf.size if cap is None else int(cap), 1), np.uint8)
+    w, h, used = _i(0), _i(0), _sz(0)
+    if not L.mdch_png_stream(_np_ptr(buf) if buf.size else None, buf.size, C.byref(w), C.byref(h), _np_ptr(out), out.size if cap is None else int(cap), C.byref(used)):
+        raise ValueError("not a PNG file the device decoder takes")
+    return w.value, h.value, out[:used.value].tobytes()
+
+
 class DatasetReader:
     """class DatasetReader (include/mono_dataset_code/BenchmarkDatasetReader.h) through the C facade."""
 
@@ -1352,6 +1452,15 @@ class DatasetReader:
     def set_gpu_jpeg(self, stage):
         """True / 2: Huffman decoding + inverse DCT on the GPU; 1: inverse DCT only; False / 0: JPEG decoded on the host."""
         self._L.mdch_reader_set_gpu_jpeg(self._h, (2 if stage else 0) if isinstance(stage, bool) else int(stage))
+
+    def set_gpu_png(self, mode):
+        """getImagesDevice on PNG frames.  True / 1: the stream classes that win go to the device decoder; 2: every eligible stream;
+        False / 0: the host decoder."""
+        self._L.mdch_reader_set_gpu_png(self._h, int(mode))
+
+    def png_device_frames(self):
+        """frames the device PNG decoder has produced for this reader"""
+        return int(self._L.mdch_reader_png_device_frames(self._h))
 
     def get_image(self, i, rectify, g, v, o):
         """-> (image (h, w) float32, timestamp, exposure, id) or None (getImage returned 0)."""

@@ -48,6 +48,15 @@ struct StreamFrames : FrameSet<const void*> {  // JPEG streams (Huffman decoding
   }
 };
 
+struct PngFrames : FrameSet<const void*> {  // zlib streams of PNG files (inflate and unfilter on the device; getImagesDevice only)
+  std::vector<long long> bytes;
+  std::vector<int> status;
+  void clear() {
+    FrameSet::clear();
+    bytes.clear();
+  }
+};
+
 // What the lanes of one call share
 struct Call {
   const BatchEnv& env;
@@ -63,6 +72,7 @@ struct Call {
   size_t rec_bytes;
   std::vector<Decode> rec;
   std::mutex image_mu;
+  const PngdApi* png;  // the device PNG decoder, where this call uses it
 };
 
 // One device of a sharded getImages call: chunks k = lane, lane + L, lane + 2L, ... of the range, each on the lane's own
@@ -91,6 +101,7 @@ struct LaneRun {
       d.cap = lane.ring_bytes;
       d.want_record_pitch = (c.env.gpu_jpeg && lane.ring_bytes >= c.rec_bytes) ? c.rec_pitch : 0;
       d.want_stream = c.env.gpu_jpeg >= 2;
+      d.want_png_stream = !c.png ? 0u : c.env.gpu_png >= 2 ? (unsigned)(kPngClassLiteral | kPngClassStored | kPngClassOther) : (unsigned)kPngDefaultClasses;
     }
     c.env.pool.submit(&c.rec[(size_t)i0], i1 - i0);
   }
@@ -99,7 +110,14 @@ struct LaneRun {
     if (!c.env.quiet)
       std::printf("ERROR: expected cv-mat to have dimensions %d x %d; found %d x %d (image %s)!\n", c.env.W, c.env.H, d.w, d.h, c.env.src.name(d.id).c_str());
     if (!d.ok) c.env.err.note(d.err);
+    if (!d.ok) chunk_errors.push_back(std::make_pair(d.id - c.first, d.err));
   }
+  // The chunk's failed frames (position, note).  A frame the device PNG decoder refuses fails after its neighbours have been looked at;
+  // with such a frame in the chunk the note of the failure at the highest position is given once more at the chunk's end, so that
+  // lastError() names the frame it names when the host decodes everything (one lane; several lanes note in the order they finish).
+  std::vector<std::pair<int, std::string> > chunk_errors;
+  bool late_failure = false;
+  std::string png_error;  // the PNG decoder's own failure: the note of a chunk that fails for it
   bool fits(const Decode& d) const { return d.ok && d.w == c.env.W && d.h == c.env.H; }
   void give_back(int i) {  // position i holds no result (any more)
     if (c.out) {
@@ -107,6 +125,91 @@ struct LaneRun {
       c.out[i] = 0;
     }
     if (c.valid) c.valid[i] = 0;
+  }
+
+  // The lane's PNG decoder, for n frames of the reader's size (0: none to be had -- the frames take the host decoder)
+  void* png_decoder(int n) {
+    if (lane.pngd && lane.pngd_frames >= n) return lane.pngd;
+    if (lane.pngd) c.png->destroy(lane.pngd);
+    lane.pngd = 0;
+    const int want = std::max(n, c.C);
+    if (c.png->create(lane.device, c.env.W, c.env.H, want, &lane.pngd) != 0) lane.pngd = 0;
+    lane.pngd_frames = lane.pngd ? want : 0;
+    return lane.pngd;
+  }
+
+  // PNG streams: inflated and unfiltered by libmdc_pngd.so into its own dense array, which the fused pass reads through the
+  // device-pointer calls -- one per run of decoded frames at consecutive positions --, straight into the caller's arrays.  A stream
+  // the device refuses (or all of them, without a decoder) goes to the host decoder, as a refused JPEG stream does.
+  int run_png(PngFrames& png, int* refused) {
+    const BatchEnv& env = c.env;
+    const mdc_device_outputs* dev = c.dev;
+    mdc_ctx* gpu = lane.gpu;
+    const int n = (int)png.n();
+    png.status.assign((size_t)n, -1);
+    const unsigned char* d_frames = 0;
+    void* dec = png_decoder(n);
+    if (dec && c.png->decode_host(dec, png.src.data(), png.bytes.data(), n, png.status.data(), &d_frames) != 0) png.status.assign((size_t)n, -1);
+    int grc = MDC_OK;
+    if (dec && d_frames) {
+      // The device-pointer calls enqueue on the stream they are given and do not wait.  This library has no HIP of its own to make or
+      // wait for a stream, and mdc_synchronize covers only the context's internal streams: the fused pass therefore runs on the decoder's
+      // stream (one per lane, so two lanes overlap) and mdci_synchronize waits for it; mdc_synchronize after it covers whatever the
+      // context put on streams of its own.
+      void* stream = c.png->stream(dec);
+      const bool rect = (c.flags & MDC_RECTIFY) != 0, grads = dev->dI[0] != 0;
+      const int w0 = rect ? env.w : env.W, h0 = rect ? env.h : env.H;
+      const size_t n_in = (size_t)env.W * env.H, n_out = (size_t)w0 * h0;
+      for (int q = 0; q < n && grc == MDC_OK;) {
+        if ((png.status[(size_t)q] & 0xffff) != 0) {
+          q++;
+          continue;
+        }
+        const int64_t pos = png.pos[(size_t)q];
+        int run = 1;
+        while (q + run < n && (png.status[(size_t)(q + run)] & 0xffff) == 0 && png.pos[(size_t)(q + run)] == pos + run) run++;
+        const uint8_t* src = d_frames + (size_t)q * n_in;
+        float* base = dev->base + (size_t)pos * n_out;
+        if (dev->levels == 1 && !grads) {
+          grc = mdc_process_batch_device(gpu, src, base, run, c.flags, stream);
+        } else {
+          float *lv[3] = {0, 0, 0}, *gi[4] = {0, 0, 0, 0}, *ga[4] = {0, 0, 0, 0};
+          for (int l = 0; l < dev->levels; l++) {
+            const size_t npl = (size_t)(w0 >> l) * (size_t)(h0 >> l);
+            if (l) lv[l - 1] = dev->level[l - 1] + (size_t)pos * npl;
+            if (grads) gi[l] = dev->dI[l] + (size_t)pos * npl * 3, ga[l] = dev->abs_squared_grad[l] + (size_t)pos * npl;
+          }
+          grc = grads ? mdc_process_pyramid_gradients_batch_device(gpu, src, base, dev->levels, lv, gi, ga, run, c.flags, 0, stream)
+                      : mdc_process_pyramid_batch_device(gpu, src, base, dev->levels, lv, run, c.flags, stream);
+        }
+        lane.png_frames += run;
+        q += run;
+      }
+      if (c.png->synchronize(dec) != 0 && grc == MDC_OK) {
+        png_error = std::string("getImagesDevice: PNG decoder: ") + c.png->last_error();
+        return MDC_ERR_HIP;
+      }
+      if (grc == MDC_OK) grc = mdc_synchronize(gpu);
+    }
+    for (int q = 0; q < n && grc == MDC_OK; q++)
+      if ((png.status[(size_t)q] & 0xffff) != 0) {  // the host decoder has the last word
+        const int64_t pos = png.pos[(size_t)q];
+        Decode one;
+        one.id = c.first + (int)pos;
+        one.dst = const_cast<unsigned char*>(static_cast<const unsigned char*>(png.src[(size_t)q]));  // the ring buffer of this frame
+        one.cap = lane.ring_bytes;
+        env.pool.decode_now(one);
+        if (fits(one)) {
+          const uint8_t* one_src = one.dst;
+          grc = mdc_process_frames_host_to_device(gpu, &one_src, 1, c.flags, dev, &pos);
+        } else {
+          bad_frame(one);
+          late_failure = true;
+          give_back((int)pos);
+          (*refused)++;
+        }
+      }
+    return grc;
   }
 
   // run() threw (out of memory for an image or a list of pointers): the images it had made for the current chunk hold no
@@ -127,6 +230,7 @@ struct LaneRun {
     PlainFrames plain;
     RecordFrames records;
     StreamFrames streams;
+    PngFrames pngs;
     for (int j = 0; j < mine; j++) {
       const int i0 = chunk_begin(j), i1 = chunk_end(j);
       const double tw = now();
@@ -137,6 +241,10 @@ struct LaneRun {
       plain.clear();
       records.clear();
       streams.clear();
+      pngs.clear();
+      chunk_errors.clear();
+      late_failure = false;
+      png_error.clear();
       {
         // a chunk's images are made in one go: the pool hands out consecutive blocks of a slab (lowest free address first),
         // and a chunk whose results lie back to back leaves the device with one copy -- another lane allocating in between
@@ -151,7 +259,10 @@ struct LaneRun {
           if (c.out) c.out[i] = new_image(env, d.id, c.rectify);
           if (c.valid) c.valid[i] = 1;
           ExposureImage* image = c.out ? c.out[i] : 0;
-          if (d.is_stream) {
+          if (d.is_png_stream) {
+            pngs.add(d.dst, image, i);
+            pngs.bytes.push_back((long long)d.stream_bytes);
+          } else if (d.is_stream) {
             streams.add(d.dst, image, i);
             streams.bytes.push_back((int64_t)d.stream_bytes);
           } else if (d.is_record) {
@@ -198,13 +309,16 @@ struct LaneRun {
             }
           }
       }
+      if (grc == MDC_OK && pngs.n()) grc = run_png(pngs, &refused);
       t_gpu += now() - tg;
+      if (late_failure && !chunk_errors.empty()) env.err.note(std::max_element(chunk_errors.begin(), chunk_errors.end())->second);
       if (grc != MDC_OK) {
-        env.err.note(mdc_last_error(gpu));
-        std::fprintf(stderr, "DatasetReader::getImages: %s\n", mdc_last_error(gpu));
+        const std::string why = png_error.empty() ? std::string(mdc_last_error(gpu)) : png_error;
+        env.err.note(why);
+        std::fprintf(stderr, "DatasetReader::getImages: %s\n", why.c_str());
         for (int i = i0; i < i1; i++) give_back(i);
       } else {
-        produced += (int)(plain.n() + records.n() + streams.n()) - refused;
+        produced += (int)(plain.n() + records.n() + streams.n() + pngs.n()) - refused;
       }
       cur_i0 = cur_i1 = 0;  // the chunk is settled: its images are results (or gone)
       if (j + c.RG < mine) submit(j + c.RG);  // the buffers of the lane's chunk j are free again
@@ -233,7 +347,7 @@ int run_batch(const BatchEnv& env, const std::vector<Lane*>& use, int first, int
   const int slots = (env.gpu_jpeg >= 2 && per_lane > 1) ? 2 * C : (env.gpu_jpeg >= 2 ? C : kRingFrames), RG = slots / C;
   const int active = std::min(L, nchunks);
   const int rec_pitch = ((env.W + 7) / 8 + 11) / 12 * 12, rec_rows = ((env.H + 7) / 8 + 11) / 12 * 12;
-  Call c = {env, first, count, C, RG, active, rectify, flags, out, dev, valid, rec_pitch, rec_rows, 128 + (size_t)rec_pitch * rec_rows * 128, {}, {}};
+  Call c = {env, first, count, C, RG, active, rectify, flags, out, dev, valid, rec_pitch, rec_rows, 128 + (size_t)rec_pitch * rec_rows * 128, {}, {}, (dev && env.gpu_png) ? pngd_api() : 0};
   // a ring buffer holds a decoded frame, or (stage 1) a coefficient record -- 2 bytes per pixel --, or (stage 2) a stream: the
   // compressed bytes + 5 KB; a file stage 2 does not take, or whose stream does not fit, is decoded to pixels on the host
   const size_t want_bytes = env.gpu_jpeg == 1 ? std::max(env.frame_bytes, c.rec_bytes) : env.frame_bytes;
@@ -290,6 +404,11 @@ int run_batch(const BatchEnv& env, const std::vector<Lane*>& use, int first, int
     for (const LaneRun& r : runs)
       std::fprintf(stderr, "DatasetReader::getImages: device %d (lane %d of %d): %d of %d frames, %d decode threads: waited %.1f ms for the decoders, %.1f ms in the GPU calls\n",
                    r.lane.device, r.li, active, r.produced, count, env.pool.threads(), r.t_wait * 1e3, r.t_gpu * 1e3);
+  if (trace && c.png) {
+    long png_frames = 0;
+    for (const LaneRun& r : runs) png_frames += r.lane.png_frames;
+    std::fprintf(stderr, "DatasetReader::getImages: %ld PNG frames decoded on the device so far\n", png_frames);
+  }
   return produced;
 }
 

@@ -18,6 +18,10 @@ namespace mdc_host {
 // chunk that frame is in, not the pipeline (two half-rings of 64 stalled on every straggler: 2.5-2.9 k frames/s)
 enum { kRingFrames = 256 };  // page-locked decode buffers of getImages (335 MB at 1280x1024, 670 MB in stage 1 and for calls of > 256 frames in stage 2; first getImages)
 
+// The classes of PNG streams (Decode::want_png_stream's bits) that getImagesDevice hands to the device decoder by default: those that beat
+// the host decoder on the same box in the same session (profiles/r06_pngd_rate.txt)
+enum { kPngClassLiteral = 1, kPngClassStored = 2, kPngClassOther = 4, kPngDefaultClasses = kPngClassLiteral };
+
 struct ErrorSink {  // lastError(): written by the caller's thread, and by the lanes of a batch call through note()
   std::string text;
   std::mutex mu;
@@ -38,6 +42,8 @@ struct BatchEnv {
   bool quiet;  // the batch behind getImage's lookahead: a frame that fails is reported when the caller asks for it
   // GPU JPEG stage: JPEG frames travel as coefficient records (2 bytes per pixel + table), the inverse DCT runs on the device
   int gpu_jpeg;  // 0: JPEG decoded on the host; 1: host Huffman + device inverse DCT; 2: device Huffman + inverse DCT
+  // device PNG decoder, getImagesDevice only: 0 PNG decoded on the host, 1 the stream classes of kPngDefaultClasses, 2 every eligible one
+  int gpu_png;
 };
 
 // The (empty) result image of frame `id`

@@ -62,6 +62,8 @@ struct DatasetReader::State {
   int frame_h() const { return W > 0 && H > 0 ? H : RH; }
   // GPU JPEG stage of getImages (batch_run.h).  Default on; MDC_GPU_JPEG=0 or setGpuJpeg(false) keeps the whole decode on the host.
   int gpu_jpeg = 2;
+  // device PNG decoder of getImagesDevice (batch_run.h).  MDC_GPU_PNG=0 or setGpuPng(false) keeps PNG on the host.
+  int gpu_png = 1;
   // getImage on a JPEG sequence read in order: after two consecutive ids the next `lookahead` frames go through the getImages
   // pipeline (Huffman decoding on the device) with the caller's switches, and the following calls hand those results out
   int lookahead = kRingFrames;  // the most; a run starts with 64 and doubles per batch (the longer the call, the less its fill and drain weigh)
@@ -82,12 +84,13 @@ struct DatasetReader::State {
     seq_last = id;
   }
   mdc_host::BatchEnv batch_env() {
-    return mdc_host::BatchEnv{src, pool, W, H, w, h, frame_bytes(), timestamps, exposures, err, quiet_batch, gpu_jpeg};
+    return mdc_host::BatchEnv{src, pool, W, H, w, h, frame_bytes(), timestamps, exposures, err, quiet_batch, gpu_jpeg, gpu_png};
   }
 };
 
 DatasetReader::DatasetReader(std::string folder) : s_(new State()) {
   if (const char* e = std::getenv("MDC_GPU_JPEG")) s_->gpu_jpeg = std::max(0, std::min(2, std::atoi(e)));
+  if (const char* e = std::getenv("MDC_GPU_PNG")) s_->gpu_png = std::max(0, std::min(2, std::atoi(e)));
   if (const char* e = std::getenv("MDC_READER_LOOKAHEAD")) s_->lookahead = std::max(0, std::min((int)kRingFrames, std::atoi(e)));
   State& s = *s_;
   s.path = folder;
@@ -205,6 +208,13 @@ void DatasetReader::setDecodeThreads(int n) {
 void DatasetReader::setResultLookahead(int frames) {
   s_->lookahead = std::max(0, std::min(frames, (int)kRingFrames));
   if (!s_->lookahead) s_->drop_ahead();
+}
+void DatasetReader::setGpuPng(bool on) { s_->gpu_png = on ? 1 : 0; }
+void DatasetReader::setGpuPngMode(int mode) { s_->gpu_png = std::max(0, std::min(2, mode)); }
+long DatasetReader::pngDeviceFrames() const {
+  long n = 0;
+  for (const mdc_host::Lane& ln : s_->dev.lanes) n += ln.png_frames;
+  return n;
 }
 void DatasetReader::setGpuJpeg(bool on) { s_->gpu_jpeg = on ? 2 : 0; }
 void DatasetReader::setGpuJpegStage(int stage) { s_->gpu_jpeg = std::max(0, std::min(2, stage)); }

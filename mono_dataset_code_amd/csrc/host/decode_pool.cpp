@@ -8,6 +8,7 @@
 
 #include "image_codecs.h"
 #include "image_codecs_internal.h"
+#include "../png_inflate_core.h"
 #include "mdc_hip.h"
 
 namespace mdc_host {
@@ -47,7 +48,24 @@ void DecodePool::decode_unguarded(Decode& d) const {
     return;
   }
   if (!src_.read(d.id, bytes, &d.err)) return;
-  d.is_record = d.is_stream = false;
+  d.is_record = d.is_stream = d.is_png_stream = false;
+  if (d.want_png_stream && bytes.size() > 8 && bytes[0] == 0x89 && bytes[1] == 'P') {  // else, and for what is not eligible: pixels, below
+    std::string why;
+    size_t used = 0;
+    if (png_stream(bytes.data(), bytes.size(), d.dst, d.cap, &used, &d.w, &d.h, &why) && used > 3) {
+      // the class, by the device decoder's own rule (csrc/png_inflate_core.h: zlib header, first block header, its code lengths): a single
+      // final dynamic block in which no distance symbol has a code; a first block that is stored; anything else
+      static thread_local pngd::Work work;
+      uint32_t data_bit = 0;
+      const int path = pngd::classify(work, d.dst, (uint32_t)std::min<size_t>(used, pngd::kMaxStreamBytes), &data_bit);
+      const unsigned cls = path == pngd::PATH_PARALLEL ? 1u : path == pngd::PATH_STORED ? 2u : 4u;
+      if (d.want_png_stream & cls) {
+        d.ok = d.is_png_stream = true;
+        d.stream_bytes = used;
+        return;
+      }
+    }
+  }
   const bool is_jpeg = bytes.size() > 4 && bytes[0] == 0xff && bytes[1] == 0xd8;
   if (d.want_stream && is_jpeg) {  // what the device decoder takes (grayscale baseline, no restart markers); else the record path
     std::string why;

@@ -35,6 +35,11 @@ struct Decode {
   // ... or, with the Huffman decoding on the GPU as well, only unstuffed into a stream (mdc_jpeg_stream_header + bytes) at dst
   bool want_stream = false, is_stream = false;
   size_t stream_bytes = 0;
+  // getImagesDevice with the device PNG decoder: an eligible PNG file (8-bit grayscale, non-interlaced, its first block of a class
+  // in the mask: bit 0 a single final dynamic block in which no distance symbol has a code, bit 1 stored, bit 2 anything else) is only walked: its zlib
+  // stream goes to dst (stream_bytes of it)
+  unsigned want_png_stream = 0;
+  bool is_png_stream = false;
   std::string err;
 
  private:

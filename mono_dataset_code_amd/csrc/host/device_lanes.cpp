@@ -38,6 +38,34 @@ bool DeviceLanes::load_multi() {
   return true;
 }
 
+const PngdApi* pngd_api() {
+  static const PngdApi* api = []() -> const PngdApi* {
+    std::string path;
+    if (const char* e = std::getenv("MDC_LIB_PNGD")) {
+      path = e;
+    } else {
+      Dl_info info;
+      if (dladdr((void*)&open_device_context, &info) && info.dli_fname) {
+        path = info.dli_fname;
+        const size_t sl = path.rfind('/');
+        path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
+      }
+      path += "libmdc_pngd.so";
+    }
+    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);  // holds a HIP module: never unmapped again
+    if (!lib) return 0;
+    static PngdApi a;
+    a.create = (int (*)(int, int, int, int, void**))dlsym(lib, "mdci_create");
+    a.destroy = (void (*)(void*))dlsym(lib, "mdci_destroy");
+    a.decode_host = (int (*)(void*, const void* const*, const long long*, int, int*, const unsigned char**))dlsym(lib, "mdci_decode_host");
+    a.last_error = (const char* (*)())dlsym(lib, "mdci_last_error");
+    a.stream = (void* (*)(void*))dlsym(lib, "mdci_stream");
+    a.synchronize = (int (*)(void*))dlsym(lib, "mdci_synchronize");
+    return a.create && a.destroy && a.decode_host && a.last_error && a.stream && a.synchronize ? &a : 0;
+  }();
+  return api;
+}
+
 // MDC_DEVICES: "all" or "0,1,..." (unset or empty: no list)
 static std::vector<int> device_list() {
   std::vector<int> devs;
@@ -177,6 +205,8 @@ std::vector<Lane*> DeviceLanes::for_batch(bool device_outputs) {
 void DeviceLanes::close() {
   for (Lane& ln : lanes) {
     ln.ring_block.release();
+    if (ln.pngd) pngd_api()->destroy(ln.pngd);
+    ln.pngd = 0;
     if ((!multi_ || ln.twin) && ln.gpu) mdc_destroy(ln.gpu);
   }
   if (multi_) mapi_.destroy(multi_);

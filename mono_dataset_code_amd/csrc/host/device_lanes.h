@@ -17,7 +17,23 @@ namespace mdc_host {
 // One lane per device the reader may use (MDC_DEVICES; lanes[0] holds the reader's public context): its context and its own decode
 // ring -- ONE page-locked block, slot i at ring_block.p + i * ring_stride (a chunk's uploads are then one strided copy instead of
 // one copy per frame), ring_bytes per buffer (a frame, or a record when the GPU JPEG stage is on).
+// libmdc_pngd.so (include/mdc_pngd.h), loaded at run time: the device PNG decoder of getImagesDevice
+struct PngdApi {
+  int (*create)(int, int, int, int, void**) = 0;
+  void (*destroy)(void*) = 0;
+  int (*decode_host)(void*, const void* const*, const long long*, int, int*, const unsigned char**) = 0;
+  const char* (*last_error)() = 0;
+  void* (*stream)(void*) = 0;
+  int (*synchronize)(void*) = 0;
+};
+// The library next to this one (or the file MDC_LIB_PNGD names), opened once per process and never closed; 0 when it is not there:
+// PNG frames then take the host decoder, silently.
+const PngdApi* pngd_api();
+
 struct Lane {
+  void* pngd = 0;  // the lane's mdci_decoder, made at first use for pngd_frames frames of the reader's size
+  int pngd_frames = 0;
+  long png_frames = 0;  // statistics: frames it decoded
   mdc_ctx* gpu = 0;
   int device = -1;
   bool twin = false;  // a second context on lane 0's device, made for getImagesDevice (ensure_device_lanes); owned by the reader

@@ -43,6 +43,10 @@ bool decode_jpeg_coefs(const unsigned char* data, size_t n, JpegCoefSink* sink, 
 // lossless files, restart intervals, 16-bit quantisation values above what a record holds, a stream that does not fit.
 bool jpeg_stream(const unsigned char* data, size_t n, unsigned char* stream, size_t cap, size_t* used, int* w, int* h, std::string* err);
 
+// The zlib stream of an 8-bit grayscale, non-interlaced PNG -- its IDAT bodies, concatenated -- copied to `stream`, for the device
+// decoder (include/mdc_pngd.h).  false: any other flavour, no IHDR, a truncated chunk, or a stream that does not fit cap.
+bool png_stream(const unsigned char* data, size_t n, unsigned char* stream, size_t cap, size_t* used, int* w, int* h, std::string* err);
+
 // The format decoders behind decode_gray8 (image_codecs.h); a JPEG decoder with a sink delivers coefficients instead of samples.
 bool png_gray8(const unsigned char* data, size_t n, unsigned char* out, size_t cap, int* w, int* h, std::string* err);
 bool jpeg_gray8(const unsigned char* data, size_t n, unsigned char* out, size_t cap, int* w, int* h, std::string* err, JpegCoefSink* sink = nullptr);

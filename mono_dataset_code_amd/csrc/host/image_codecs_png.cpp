@@ -137,6 +137,22 @@ bool png_gray8(const unsigned char* d, size_t n, unsigned char* out, size_t cap,
   return true;
 }
 
+bool png_stream(const unsigned char* d, size_t n, unsigned char* stream, size_t cap, size_t* used, int* w, int* h, std::string* err) {
+  static thread_local std::vector<unsigned char> idat;
+  idat.clear();
+  if (n < 8 || memcmp(d, "\x89PNG\r\n\x1a\n", 8) != 0) return fail(err, "PNG: no signature");
+  const PngChunks c = png_chunks(d, n, idat, nullptr);
+  if (c.truncated) return fail(err, "PNG: truncated chunk");
+  if (!c.have_ihdr || c.W == 0 || c.H == 0 || c.W > 65535 || c.H > 65535) return fail(err, "PNG: no IHDR");
+  if (c.ctype != 0 || c.depth != 8 || c.interlace != 0) return fail(err, "PNG: not 8-bit grayscale, non-interlaced");
+  if (!stream || idat.size() > cap) return fail(err, "PNG: the stream does not fit the buffer");
+  if (!idat.empty()) memcpy(stream, idat.data(), idat.size());
+  *used = idat.size();
+  *w = (int)c.W;
+  *h = (int)c.H;
+  return true;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // PNG, general
 // ---------------------------------------------------------------------------------------------------------

@@ -280,6 +280,8 @@ void mdch_reader_raw_dims(mdch_reader* h, int wh[2]) try { h->r->getRawSize(&wh[
 void mdch_reader_set_threads(mdch_reader* h, int n) try { h->r->setDecodeThreads(n); } catch (...) {}
 void mdch_reader_set_prefetch(mdch_reader* h, int n) try { h->r->setPrefetch(n); } catch (...) {}
 void mdch_reader_set_lookahead(mdch_reader* h, int frames) try { h->r->setResultLookahead(frames); } catch (...) {}
+void mdch_reader_set_gpu_png(mdch_reader* h, int mode) try { h->r->setGpuPngMode(mode); } catch (...) {}
+long mdch_reader_png_device_frames(mdch_reader* h) try { return h->r->pngDeviceFrames(); } catch (...) { return {}; }
 void mdch_reader_set_gpu_jpeg(mdch_reader* h, int stage) try { h->r->setGpuJpegStage(stage == 1 ? 1 : (stage ? 2 : 0)); } catch (...) {}
 const char* mdch_reader_last_error(mdch_reader* h) try { return h->r->lastError(); } catch (...) { return {}; }
 void mdch_reader_prefetch_stats(mdch_reader* h, long hm[2]) try { h->r->getPrefetchStats(&hm[0], &hm[1]); } catch (...) {}
@@ -329,6 +331,12 @@ int mdch_decode_jpeg_record(const unsigned char* data, size_t n, void* record, s
     err[errcap - 1] = 0;
   }
   return ok ? 1 : 0;
+} catch (...) { return {}; }  // no exception leaves the C facade
+
+int mdch_png_stream(const unsigned char* file, size_t bytes, int* w, int* h, unsigned char* dst, size_t cap, size_t* stream_bytes) try {
+  if (!file || !w || !h || !dst || !stream_bytes) return 0;
+  std::string e;
+  return mdc_host::png_stream(file, bytes, dst, cap, stream_bytes, w, h, &e) ? 1 : 0;
 } catch (...) { return {}; }  // no exception leaves the C facade
 
 long long mdch_jpeg_stream(const unsigned char* data, size_t n, void* stream, size_t cap, int wh[2], char* err, size_t errcap) try {
