@@ -114,7 +114,14 @@ enum { MDC_OPT_KERNEL = 1, MDC_OPT_FRAMES_PER_BLOCK = 2 /* frames a workgroup lo
           nor MDC_PIPE_DEV_CHUNK is set (the reader gives 128 to the contexts it runs two lanes on); 0 = no hint */,
        MDC_OPT_TAIL_TAPER = 15 /* tuning: a large launch of the tiled kernel ends on frame groups of 1/2, 1/4 and 1/8 of the
           frames per workgroup, so the slots that free up when its last long workgroups finish do not idle for a long
-          workgroup's time: 0 = automatic (on), 1 = on, 2 = off */ };
+          workgroup's time: 0 = automatic (on), 1 = on, 2 = off */,
+       MDC_OPT_XCD_ROTATE = 18 /* tuning: frame group y of a remap launch shifts the placement of the tiles on the 8 XCDs by y, so an
+          XCD whose share of the tiles is short (75 tiles: 10/.../10/5) is a different one in every group and all eight carry the
+          same load over a launch; the bands of MDC_ORDER_BANDS become an even split (9/10).  Applies to all MDC_ORDER_* modes.
+          0 = off (each XCD runs the same tiles in every group), 1 = on for the workgroup-tiled kernels (the default: 2.4-3.3 % faster
+          on the 4096-frame headline launch and on the 50,000-frame sequence), 2 = on for the wave-private strip kernel as well
+          (MDC_OPT_TWO_STAGE; measured 2.8 % slower on config 5, whose chunks hold two frame groups: kept for measurement;
+          profiles/r07_experiments/01_*) */ };
 enum { MDC_ORDER_BANDS = 0 /* row-major runs of tiles per XCD */, MDC_ORDER_ROWS = 1 /* whole tile rows per XCD */,
        MDC_ORDER_IDENTITY = 2 /* block b = tile b (diagnosis) */,
        MDC_ORDER_BLOCKS2D = 3 /* the tile grid cut into 8 rectangles, one per XCD */ };

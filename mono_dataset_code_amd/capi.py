@@ -24,6 +24,7 @@ OPT_PREFETCH_CHUNK = 12
 OPT_PREFETCH_STREAMS = 13
 OPT_ZERO_COPY = 14
 OPT_TAIL_TAPER = 15
+OPT_XCD_ROTATE = 18
 OPT_DEVICE_PIPELINE_CHUNK, OPT_DEVICE_PIPELINE_CHUNK_HINT = 16, 17
 ORDER_BANDS, ORDER_ROWS, ORDER_IDENTITY, ORDER_BLOCKS2D = 0, 1, 2, 3
 OK, ERR_ARG, ERR_STATE, ERR_SIZE, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6

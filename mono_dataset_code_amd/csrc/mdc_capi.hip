@@ -99,7 +99,7 @@ int frames_per_block(const mdc_ctx* c, int64_t nframes, int blocks_per_group, in
 TilePlan tile_plan(const mdc_ctx* c, int which) {
   const mdc_ctx::SrcPlan& pl = c->plan[which];
   return TilePlan{pl.d_chunks, pl.d_nch, pl.d_taps, pl.d_order, pl.n_blocks, pl.n_tiles, pl.tiles_x, pl.tile_w, pl.tile_h,
-                  pl.chunk_cap, pl.win_bytes, pl.nbuf, c->n_black > 0, c->opt_interleave != 0, c->opt_taper != 2};
+                  pl.chunk_cap, pl.win_bytes, pl.nbuf, c->n_black > 0, c->opt_interleave != 0, c->opt_taper != 2, c->opt_xcd_rotate != 0};
 }
 
 RemapArgs remap_args(const mdc_ctx* c, const float* lut, const float* vinv) {
@@ -182,7 +182,7 @@ int enqueue_process(mdc_ctx* c, const uint8_t* d_in, float* d_out, int64_t nfram
   if (c->strip.planned && aligned && c->opt_kernel != MDC_KERNEL_GATHER) {  // wave-private strips (scale >= ~1 remaps)
     const mdc_ctx::Strip& st = c->strip;
     const StripPlan sp{st.d_chunks, st.d_nch, st.d_taps, st.d_order, st.n_blocks, st.n_tiles, st.tiles_x, st.win_bytes, st.passes, st.nbuf,
-                       c->opt_interleave != 0};
+                       c->opt_interleave != 0, c->opt_xcd_rotate == 2};
     const bool fuse_pyr = pyr && c->out_w % kStripTileW == 0;
     // Large batches go in chunks, each preceded by a linear prefetch of the NEXT chunk's source rows into the Infinity
     // Cache (launch_prefetch_rows): the strips' small window reads then hit the cache instead of interrupting the output
@@ -582,6 +582,16 @@ int mdc_set_option(mdc_ctx* c, int option, int value) try {
       if (value < MDC_ORDER_BANDS || value > MDC_ORDER_BLOCKS2D) return fail(c, MDC_ERR_ARG, "bad tile order %d", value);
       if (value == c->opt_order) return MDC_OK;
       c->opt_order = value;
+      if (!c->valid_remap) return MDC_OK;
+      DeviceGuard dg(c->device);
+      MDC_HIP(c, hipDeviceSynchronize());
+      return plan_tiles(c);
+    }
+    case MDC_OPT_XCD_ROTATE: {
+      if (value < 0 || value > 2) return fail(c, MDC_ERR_ARG, "XCD rotation must be 0 (off), 1 (on) or 2 (on, strip kernel included)");
+      if (value == c->opt_xcd_rotate) return MDC_OK;
+      c->opt_xcd_rotate = value;
+      c->tuned_fpb = 0;
       if (!c->valid_remap) return MDC_OK;
       DeviceGuard dg(c->device);
       MDC_HIP(c, hipDeviceSynchronize());

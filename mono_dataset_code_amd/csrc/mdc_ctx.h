@@ -101,6 +101,7 @@ struct mdc_ctx {
   int opt_tile_h = 0;  // 0 = automatic: the first shape of the candidate list whose windows fit
   int opt_tile_w = 0;  // 0 = automatic
   int opt_order = MDC_ORDER_BANDS;
+  int opt_xcd_rotate = 1;  // MDC_OPT_XCD_ROTATE: frame group y shifts the tiles' XCDs by y (xcd_placement.h); 1 = tiled kernels (2.4-3.3 % faster), 2 = strip kernel too (2.8 % slower)
   int opt_nbuf = 0;  // 0 = automatic
   int opt_interleave = 0;
   int opt_pin_caller = 0;  // MDC_OPT_PIN_CALLER_BUFFERS

@@ -6,6 +6,7 @@
 
 #include "fov_point_model.h"
 #include "mdc_build_config.h"
+#include "xcd_placement.h"
 
 namespace mdc {
 
@@ -58,6 +59,7 @@ struct TilePlan {
   bool has_black;  // some output carries the (-1,-1) sentinel
   bool interleave; // frame groups take every G-th frame instead of fpb consecutive ones
   bool taper = true;  // large launches end on frame groups of fpb/2, fpb/4, fpb/8 (MDC_OPT_TAIL_TAPER)
+  bool rotate = false;  // block (x, y) reads entry xcd_table_entry(x, y, true) of d_order (MDC_OPT_XCD_ROTATE, xcd_placement.h)
 };
 
 // Plan of the wave-private strip kernel (remap_strip_kernel): a WAVE owns a 128 x 8 output tile (lane l: columns l and
@@ -76,6 +78,7 @@ struct StripPlan {
   int passes;                // convert passes per frame (64 dwords each): 2, 3, 4, 5 or 8
   int nbuf;                  // u8 windows per wave: 1 or 2
   bool interleave;
+  bool rotate = false;       // as TilePlan::rotate
 };
 #if MDC_EXP_STRIP_FAKE_GRAD
 extern float* g_fake_grad_dI;

@@ -267,8 +267,10 @@ __global__ __launch_bounds__(256) void remap_gather_f32_kernel(const float* __re
 // XCD placement: the dispatcher deals workgroups round-robin over the 8 XCDs
 // (block b -> XCD b%8).  The host hands over a table block -> tile (TilePlan::d_order)
 // built so that each XCD owns a contiguous band of tiles; neighbouring tiles share
-// source-window halo lines, which then hit in the same L2.  Speed only --
-// correctness does not depend on placement.
+// source-window halo lines, which then hit in the same L2.  With TilePlan::rotate
+// frame group y reads the table shifted by y columns, so the XCDs take the bands
+// (and the padding slots of the short ones) in turn.  Speed only -- correctness
+// does not depend on placement.
 // ----------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 // Window buffers are handled as LDS-address-space (32-bit) pointers throughout: a generic pointer would cost a
@@ -686,7 +688,8 @@ __global__ __launch_bounds__(NT, (NT >= 960 ? 8 : NT == 640 ? 5 : NT == 512 ? (k
   float* s_lut = reinterpret_cast<float*>(smem);
   lds_u8_ptr s_win = (lds_u8_ptr)smem + (F32 ? 0 : kLutBytes);
 
-  const int tile = p.d_order[blockIdx.x];  // host-made placement table (plan_tiles); -1 = padding slot
+  // host-made placement table (plan_tiles), rotated by the frame group where asked (xcd_placement.h); -1 = padding slot
+  const int tile = p.d_order[xcd_table_entry((int)blockIdx.x, (int)blockIdx.y, p.rotate)];
   if (tile < 0) return;                    // whole workgroup leaves before any barrier
   // Frames of this workgroup: group g of G takes frames [g*fpb, (g+1)*fpb), or -- interleaved --
   // frames g, g+G, g+2G, ...  Interleaved, the groups resident at one time (dispatched in order)
@@ -892,7 +895,7 @@ __global__ __launch_bounds__(64 * W, ((PYR || P > 5 || NBUF > 2) ? MDC_EXP_STRIP
   float* s_lut = reinterpret_cast<float*>(smem + W * per_wave);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int group = p.d_order[blockIdx.x];
+  const int group = p.d_order[xcd_table_entry((int)blockIdx.x, (int)blockIdx.y, p.rotate)];
   // the LUT is filled by the whole workgroup before anybody leaves
   fill_lut_rep<64 * W, kStripLutRep>(s_lut, a.lut, tid);
   __syncthreads();

@@ -3,63 +3,7 @@
 #include "mdc_ctx.h"
 
 namespace mdc {
-// Placement table of the tiled kernel: entry b = tile run by block b of a frame group, -1 = none.
-// The dispatcher deals blocks round-robin over the 8 XCDs (block b -> XCD b % 8, slot b / 8), so
-// XCD k runs the tiles of entries k, k+8, k+16, ...  Neighbouring tiles share source lines (halo
-// rows, 128-byte lines straddling a tile border); they should meet in ONE XCD's L2.
-//   MDC_ORDER_BANDS     row-major runs of ceil(n/8) tiles per XCD
-//   MDC_ORDER_ROWS      whole tile rows per XCD, as even as the row count allows (no horizontal
-//                       neighbours split; XCDs with a row less idle at the end of a frame group)
-//   MDC_ORDER_IDENTITY  block b = tile b: neighbours land on different XCDs (diagnosis: worst case)
-//   MDC_ORDER_BLOCKS2D  the tile grid cut into 8 rectangles by recursive bisection of the longer side
-//                       (least shared halo perimeter between XCDs; the rectangles differ in size by up to
-//                       one row / column, XCDs with fewer tiles get padding slots)
-static void bisect(int x0, int y0, int x1, int y1, int parts, int tx, std::vector<std::vector<int>>& out) {
-  if (parts == 1) {
-    std::vector<int> v;
-    for (int y = y0; y < y1; y++)
-      for (int x = x0; x < x1; x++) v.push_back(y * tx + x);
-    out.push_back(v);
-    return;
-  }
-  if (x1 - x0 > y1 - y0) {
-    const int xm = x0 + (x1 - x0 + 1) / 2;
-    bisect(x0, y0, xm, y1, parts / 2, tx, out);
-    bisect(xm, y0, x1, y1, parts / 2, tx, out);
-  } else {
-    const int ym = y0 + (y1 - y0 + 1) / 2;
-    bisect(x0, y0, x1, ym, parts / 2, tx, out);
-    bisect(x0, ym, x1, y1, parts / 2, tx, out);
-  }
-}
-
-std::vector<int> tile_order(int tx, int ty, int mode) {
-  const int n = tx * ty;
-  std::vector<std::vector<int>> per_xcd(8);
-  if (mode == MDC_ORDER_BLOCKS2D && tx * ty >= 8) {
-    per_xcd.clear();
-    bisect(0, 0, tx, ty, 8, tx, per_xcd);
-  } else if (mode == MDC_ORDER_IDENTITY) {
-    for (int t = 0; t < n; t++) per_xcd[t % 8].push_back(t);
-  } else if (mode == MDC_ORDER_ROWS && ty >= 8) {
-    int r = 0;
-    for (int k = 0; k < 8; k++) {
-      const int rows = ty / 8 + (k < ty % 8 ? 1 : 0);
-      for (int y = r; y < r + rows; y++)
-        for (int x = 0; x < tx; x++) per_xcd[k].push_back(y * tx + x);
-      r += rows;
-    }
-  } else {
-    const int per = (n + 7) / 8;
-    for (int t = 0; t < n; t++) per_xcd[t / per].push_back(t);
-  }
-  size_t slots = 0;
-  for (const auto& v : per_xcd) slots = std::max(slots, v.size());
-  std::vector<int> order(slots * 8, -1);
-  for (int k = 0; k < 8; k++)
-    for (size_t j = 0; j < per_xcd[k].size(); j++) order[j * 8 + k] = per_xcd[k][j];
-  return order;
-}
+// (the placement table block -> tile, tile_order(), and the entry a block reads of it: xcd_placement.h)
 
 // Plan of the tiled kernel (see TilePlan): per tile the exact source window as a list of
 // 16-byte chunks, per output the LDS offsets of its two tap rows.  Fails (tiled = false)
@@ -203,7 +147,7 @@ int plan_source(mdc_ctx* c, int es, int kTileW, int kTileH, mdc_ctx::SrcPlan& pl
   if ((rc = upload(c, &pl.d_chunks, flat)) != MDC_OK || (rc = upload(c, &pl.d_nch, nch)) != MDC_OK ||
       (rc = upload(c, &pl.d_taps, taps)) != MDC_OK)
     return rc;
-  const std::vector<int> order = tile_order(tx, ty, c->opt_order);
+  const std::vector<int> order = tile_order(tx, ty, c->opt_order, c->opt_xcd_rotate != 0);
   if ((rc = upload(c, &pl.d_order, order)) != MDC_OK) return rc;
   pl.n_blocks = (int)order.size();
   pl.n_tiles = n_tiles;
@@ -299,7 +243,8 @@ int plan_strip(mdc_ctx* c) {
   // groups of kStripWaves consecutive tiles (row-major: neighbours along a tile row); XCD placement as for the workgroup tiles
   const int n_groups = (n_tiles + kStripWaves - 1) / kStripWaves;
   const int gx = std::max(1, tx / kStripWaves);
-  const std::vector<int> order = (tx % kStripWaves == 0) ? tile_order(gx, n_groups / gx, c->opt_order) : tile_order(n_groups, 1, MDC_ORDER_BANDS);
+  const bool rot = c->opt_xcd_rotate == 2;  // the strips rotate on request only: measured 2.8 % slower on config 5 (profiles/r07_experiments/01_*)
+  const std::vector<int> order = (tx % kStripWaves == 0) ? tile_order(gx, n_groups / gx, c->opt_order, rot) : tile_order(n_groups, 1, MDC_ORDER_BANDS, rot);
   if ((rc = upload(c, &st.d_order, order)) != MDC_OK) return rc;
   st.n_blocks = (int)order.size();
   st.n_tiles = n_tiles;

@@ -61,6 +61,7 @@ def main():
     ap.add_argument("--shapes", default="", help="tile shapes as COLSxROWS,... (overrides the --cols x --rows product), e.g. 128x16,320x16,640x8")
     ap.add_argument("--pad", default="0", help="LDS row pitch padded to 128 bytes: 0 / 1")
     ap.add_argument("--order", default="0", help="tile placement: 0 bands, 1 whole rows per XCD, 2 identity")
+    ap.add_argument("--rot", default="-1", help="XCD rotation (MDC_OPT_XCD_ROTATE): -1 library default, 0 off, 1 on, 2 on in the strip kernel too")
     ap.add_argument("--sched", default="-1", help="frame assignment: -1 library default, 0 consecutive runs, 1 interleaved")
     ap.add_argument("--nbuf", default="0", help="LDS window buffers (0 = automatic)")
     ap.add_argument("--remap", default="fov", choices=["fov", "affine", "affine128"],
@@ -137,10 +138,10 @@ def main():
     ints = lambda x: [int(v) for v in x.split(",")]  # noqa: E731
     if a.shapes:
         shp = [tuple(int(v) for v in x.split("x")) for x in a.shapes.split(",")]
-        variants = [(l, k, f, r, o, sc, nb, c, pd) for l, k, f, (c, r), o, sc, nb, pd in
-                    itertools.product(libs, a.kernel.split(","), ints(a.fpb), shp, ints(a.order), ints(a.sched), ints(a.nbuf), ints(a.pad))]
+        variants = [(l, k, f, r, o, sc, nb, c, pd, ro) for l, k, f, (c, r), o, sc, nb, pd, ro in
+                    itertools.product(libs, a.kernel.split(","), ints(a.fpb), shp, ints(a.order), ints(a.sched), ints(a.nbuf), ints(a.pad), ints(a.rot))]
     else:
-        variants = list(itertools.product(libs, a.kernel.split(","), ints(a.fpb), ints(a.rows), ints(a.order), ints(a.sched), ints(a.nbuf), ints(a.cols), ints(a.pad)))
+        variants = list(itertools.product(libs, a.kernel.split(","), ints(a.fpb), ints(a.rows), ints(a.order), ints(a.sched), ints(a.nbuf), ints(a.cols), ints(a.pad), ints(a.rot)))
     times = {v: [] for v in variants}
     same, ref_out = {}, None
     # DVFS: the first ~30 ms after an idle period run ~15 % slow (profiles/r01_dvfs_warmup_curve.txt)
@@ -160,6 +161,8 @@ def main():
             if v[5] >= 0:
                 try_set(m, ctx, "OPT_FRAME_INTERLEAVE", v[5])
             try_set(m, ctx, "OPT_WINDOW_BUFFERS", v[6])
+            if v[9] >= 0:
+                try_set(m, ctx, "OPT_XCD_ROTATE", v[9])
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ctx.process_batch(d_in.data_ptr(), d_out.data_ptr(), B, flags, s)
             if r and a.settle > 0:  # back to steady clocks after the re-plan's idle gap (the ~30 ms after one run 8 % slow: r06 experiment 06)
@@ -184,11 +187,11 @@ def main():
             torch.cuda.synchronize()
             if r:
                 times[v].append(e0.elapsed_time(e1) / a.iters)
-    print("%-28s %-7s %5s %4s %4s %3s %3s %3s %3s %10s %10s %9s %7s" % ("lib", "kernel", "fpb", "cols", "rows", "ord", "sch", "buf", "pad", "median_ms", "min_ms", "GB/s", "frac8T") + "  ==first")
+    print("%-28s %-7s %5s %4s %4s %3s %3s %3s %3s %3s %10s %10s %9s %7s" % ("lib", "kernel", "fpb", "cols", "rows", "ord", "sch", "buf", "pad", "rot", "median_ms", "min_ms", "GB/s", "frac8T") + "  ==first")
     for v in variants:
         med, mn = float(np.median(times[v])), float(np.min(times[v]))
         gbs = alg * B / (med * 1e-3) / 1e9
-        print("%-28s %-7s %5d %4d %4d %3d %3d %3d %3d %10.4f %10.4f %9.1f %7.3f" % (os.path.basename(v[0])[-28:], v[1], v[2], v[7], v[3], v[4], v[5], v[6], v[8], med, mn, gbs, gbs / 8000) + "  " + str(same.get(v)), flush=True)
+        print("%-28s %-7s %5d %4d %4d %3d %3d %3d %3d %3d %10.4f %10.4f %9.1f %7.3f" % (os.path.basename(v[0])[-28:], v[1], v[2], v[7], v[3], v[4], v[5], v[6], v[8], v[9], med, mn, gbs, gbs / 8000) + "  " + str(same.get(v)), flush=True)
     if not all(same.values()):
         print("RESULTS DIFFER between variants")
         sys.exit(1)
