@@ -542,6 +542,23 @@ MDC_API int mdc_vcal_plane_coords_device(mdc_ctx* ctx, const mdc_fov_model* mode
 MDC_API int mdc_vcal_smooth_device(mdc_ctx* ctx, const float* d_vignette_factor, int w, int h, float* d_smoothed, float* d_scratch,
                            void* stream);
 
+/* The result images of vignetteCalib (:72-94, :568-583), rendered on the device for include/mdc_pngw.h and include/mdc_pngw_rgb.h to write.  Both calls
+ * synchronise `stream`.  The float -> integer conversions are the ones OpenCV's source prescribes (DESIGN.md section 7c names the
+ * places); they have not been run against OpenCV.
+ *
+ * mdc_vcal_plot_plane_device: displayImage (:72-94) of the gw x gh plane colours -> d_rgb, gw*gh*3 bytes in FILE order R, G, B
+ * (what plane.png holds; the reference builds B, G, R and OpenCV swaps on write).  vmin / vmax are float, start from 1e10f /
+ * -1e10f and are replaced under `vmin > I[i]` / `vmax < I[i]` only: a NaN is never taken, of equal values the first in index
+ * order stays (so a zero keeps its sign).  range_host[2] (host) receives vmin, vmax, which the reference prints.  Every component
+ * is (unsigned char)((255 * (I[i] - vmin)) / (vmax - vmin)) in float, product first, truncated as x86 converts (a NaN quotient,
+ * vmax == vmin, gives 0); a NaN pixel is (255, 0, 0).  gw * gh < 2^31.
+ *
+ * mdc_vcal_vignette_u16_device: d_out[i] = saturate_cast<ushort>(cvRound(I[i] * s)), s = (float)(254.9 * 254.9) with the product
+ * formed in double: rintf (ties to even), clamped to 0..65535, NaN -> 0 -- the 16-bit pixels of vignette.png and
+ * vignetteSmoothed.png (:570-572, :578-580).  n is 64-bit; d_vignette 4-byte and d_out 2-byte aligned. */
+MDC_API int mdc_vcal_plot_plane_device(mdc_ctx* ctx, const float* d_plane, int gw, int gh, uint8_t* d_rgb, float* range_host, void* stream);
+MDC_API int mdc_vcal_vignette_u16_device(mdc_ctx* ctx, const float* d_vignette, int64_t n, uint16_t* d_out, void* stream);
+
 /* ---- responseCalib solver (src/main_responseCalib.cpp:177-380) --------------------------------------- */
 
 /* An exposure sweep on the device: d_images = n_images stacked w x h 8-bit frames (what getImageRaw gives, e.g. through
@@ -608,6 +625,26 @@ typedef struct mdc_rcal_log {
 } mdc_rcal_log;
 MDC_API int mdc_rcal_solve_device(mdc_ctx* ctx, const uint8_t* d_images, const double* d_exposure, int n_images, int w, int h,
                           int iterations, unsigned mode, double* d_G, double* d_E, mdc_rcal_log* log, void* stream);
+/* The result images of responseCalib (plotE / plotG, :72-146), rendered on the device for include/mdc_pngw.h and include/mdc_pngw_rgb.h to write.  Both calls
+ * synchronise `stream` and follow the reference's expression order (no contraction).  Minima and maxima start from 1e10 / -1e10
+ * and are replaced under `<` / `>` only: a NaN is never taken, an all-NaN input leaves the start values, and of equal values the
+ * first in index order stays (so a zero keeps its sign in the printed "%f").
+ *
+ * mdc_rcal_plot_e_device: plotE of d_E (w*h doubles).  d_rgb: w*h*3 bytes in FILE order R, G, B (what E-k.png holds; the reference
+ * builds B, G, R and OpenCV swaps on write): with le = log(E[i] + 20), min / max over le, float val = 3 * (exp((le - min) /
+ * (max - min)) - 1) / 1.7183 (double, narrowed once), icP = (int)val, ifP = val - icP, icP %= 3 and c = (unsigned char)(255 * ifP),
+ * the pixel is (c, 0, 0), (255, c, 0), (255, 255, c) for icP 0, 1, 2, and black for a NaN val (x86's (int)NaN is INT_MIN, no
+ * branch fires, cv::Vec3b() is zeros) -- a NaN E[i], or max == min.  d_e16[i] = (unsigned short)(255 * 255 * (E[i] - Emin) /
+ * (Emax - Emin)), the low 16 bits of x86's double -> int conversion (NaN -> 0): what E-k16.png holds.  range_host[2] (host)
+ * receives Emin, Emax, which the reference prints as "Irradiance %f - %f".  w * h < 2^31; d_e16 2-byte aligned.
+ *
+ * mdc_rcal_plot_g_device: plotG of d_G (256 doubles) -> d_img, 256 x 256 floats, row k, column i: with val = 256 * (G[i] - min) /
+ * (max - min), (float)(k - val) * 255.0f where val < k, else 0 (a NaN val gives 0) -- the floats cv::imwrite receives from
+ * GImg * 255; mdcp_encode_f32_device then rounds them as OpenCV's convertTo(CV_8U) does.  range_host[2] receives min, max
+ * ("Inv. Response %f - %f"). */
+MDC_API int mdc_rcal_plot_e_device(mdc_ctx* ctx, const double* d_E, int w, int h, uint8_t* d_rgb, uint16_t* d_e16, double* range_host,
+                           void* stream);
+MDC_API int mdc_rcal_plot_g_device(mdc_ctx* ctx, const double* d_G, float* d_img, double* range_host, void* stream);
 /* Blocking copy to device memory of the context's GPU from host or device memory (the counterpart of mdc_copy_to_host). */
 MDC_API int mdc_copy_to_device(mdc_ctx* ctx, void* d_dst, const void* src, size_t bytes);
 

@@ -24,7 +24,7 @@ LIB_HOST = os.path.join(PKG, "libmdc_host.so")
 
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("mdc_kernels.hip", "mdc_vcal.hip", "mdc_jpeg.hip", "mdc_capi.hip", "mdc_plan.hip", "mdc_host_calls.hip",
                                                 "mdc_pipeline.hip", "mdc_placement.hip", "mdc_rcal.hip")]
-HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "mdc_exports.map"), os.path.join(CSRC, "mdc_internal.h"), os.path.join(CSRC, "mdc_ctx.h"), os.path.join(CSRC, "mdc_build_config.h"), os.path.join(CSRC, "fov_point_model.h"), os.path.join(CSRC, "placement_classes.h"), os.path.join(CSRC, "xcd_placement.h"), os.path.join(INC, "mdc_hip.h")]
+HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "mdc_exports.map"), os.path.join(CSRC, "mdc_internal.h"), os.path.join(CSRC, "mdc_ctx.h"), os.path.join(CSRC, "mdc_build_config.h"), os.path.join(CSRC, "fov_point_model.h"), os.path.join(CSRC, "minmax_first.h"), os.path.join(CSRC, "placement_classes.h"), os.path.join(CSRC, "xcd_placement.h"), os.path.join(INC, "mdc_hip.h")]
 HOST_SOURCES = [os.path.join(HOST, f) for f in (
     "fov_undistorter.cpp", "photometric_undistorter.cpp", "gray_png.cpp", "host_device.cpp", "mdc_host_capi.cpp",
     "image_codecs.cpp", "image_codecs_png.cpp", "image_codecs_jpeg.cpp", "image_codecs_jpeg_stream.cpp", "zip_reader.cpp", "image_pool.cpp", "frame_source.cpp", "decode_pool.cpp",
@@ -203,7 +203,8 @@ RECTIFY_DATASET_SOURCE = os.path.join(CSRC, "programs", "rectifyDataset.cpp")
 
 
 def build_programs(force=False):
-    """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so;
+    """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so, and libmdc_pngw.so /
+    libmdc_pngw_rgb.so for its result images;
     bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so;
     bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those, libmdc_zipw.so
     and libmdc_pngw.so."""
@@ -211,11 +212,15 @@ def build_programs(force=False):
     build_jenc(force)
     build_zipw(force)
     build_pngw(force)
+    build_pngw_rgb(force)
     os.makedirs(BIN, exist_ok=True)
-    deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
+    deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, LIB_PNGW, LIB_PNGW_RGB, LIB_ZIPW, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_pngw.h"),
+            os.path.join(INC, "mdc_pngw_rgb.h"),
+            os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RESPONSE_CALIB, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
-              RESPONSE_CALIB_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-Wl,-rpath,$ORIGIN/..", "-o", RESPONSE_CALIB])
+              RESPONSE_CALIB_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_zipw", "-lmdc_pngw", "-lmdc_pngw_rgb", "-Wl,-rpath,$ORIGIN/..", "-o",
+              RESPONSE_CALIB])
     deps = [PLAY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
             os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(PLAY_DATASET, deps):
@@ -282,6 +287,22 @@ def build_pngw(force=False):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGW_EXPORT_MAP, "-o", LIB_PNGW])
     return LIB_PNGW
+
+
+LIB_PNGW_RGB = os.path.join(PKG, "libmdc_pngw_rgb.so")
+PNGW_RGB_EXPORT_MAP = os.path.join(CSRC, "mdc_pngw_rgb_exports.map")
+
+
+def build_pngw_rgb(force=False):
+    """libmdc_pngw_rgb.so: the device PNG encoder for 8-bit RGB images (include/mdc_pngw_rgb.h) -- mdc_pngw.hip built with
+    -DMDCP_RGB8_LIBRARY, a library of its own beside libmdc_pngw.so (which stays what it is), on top of libmdc_zipw.so."""
+    build_zipw(force)
+    if force or _stale(LIB_PNGW_RGB, [PNGW_SOURCE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pngw_rgb.h"), os.path.join(INC, "mdc_zipw.h"),
+                                      PNGW_RGB_EXPORT_MAP, LIB_ZIPW]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-DMDCP_RGB8_LIBRARY=1", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN",
+              "-Wl,--version-script=" + PNGW_RGB_EXPORT_MAP, "-o", LIB_PNGW_RGB])
+    return LIB_PNGW_RGB
 
 
 LIB_PNGD = os.path.join(PKG, "libmdc_pngd.so")
@@ -380,6 +401,7 @@ def build_all(force=False):
     build_jenc(force)
     build_zipw(force)
     build_pngw(force)
+    build_pngw_rgb(force)
     build_pngd(force)
     build_debug()
     build_fault_injection()

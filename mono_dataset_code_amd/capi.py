@@ -183,6 +183,8 @@ HIP_API = {  # include/mdc_hip.h (libmdc_hip.so)
     "mdc_vcal_mask_coords_device": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "mdc_vcal_plane_coords_device": (_i, [_vp, _P(FovModel), _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "mdc_vcal_smooth_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mdc_vcal_plot_plane_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mdc_vcal_vignette_u16_device": (_i, [_vp, _vp, _i64, _vp, _vp]),
     # ---- responseCalib solver
     "mdc_rcal_leak_pad_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mdc_rcal_init_e_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -197,6 +199,8 @@ HIP_API = {  # include/mdc_hip.h (libmdc_hip.so)
     "mdc_rcal_e_step_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mdc_rcal_rescale_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mdc_rcal_solve_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _u, _vp, _vp, _P(RcalLog), _vp]),
+    "mdc_rcal_plot_e_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mdc_rcal_plot_g_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mdc_copy_to_device": (_i, [_vp, _vp, _vp, _sz]),
     # ---- plan selection by measurement, diagnostics
     "mdc_tune_device": (_i, [_vp, _vp, _vp, _i64, _u, _vp, _P(TuneResult)]),
@@ -309,6 +313,14 @@ PNGW_API = {  # include/mdc_pngw.h (libmdc_pngw.so: the device PNG encoder, a li
     "mdcp_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
     "mdcp_huffman_lengths_device": (_i, [_vp, _i, _i, _vp, _vp]),
 }
+PNGW_RGB_API = {  # include/mdc_pngw_rgb.h (libmdc_pngw_rgb.so: the same encoder built for 8-bit RGB images, a library of its own)
+    "mdcp_png_bound_rgb8": (_i64, [_i, _i]),
+    "mdcp_last_error_rgb8": (_cp, []),
+    "mdcp_create_rgb8": (_i, [_i, _i, _i, _i, _i, _P(_vp)]),
+    "mdcp_destroy_rgb8": (None, [_vp]),
+    "mdcp_encode_rgb8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcp_output_device_rgb8": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
+}
 PNGD_API = {  # include/mdc_pngd.h (libmdc_pngd.so: the device PNG decoder, a library of its own)
     "mdci_last_error": (_cp, []),
     "mdci_scratch_bytes": (_i64, [_i, _i, _i]),
@@ -327,6 +339,7 @@ LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
 LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
 LIB_ZIPW_PATH = os.path.join(_PKG, "libmdc_zipw.so")
 LIB_PNGW_PATH = os.path.join(_PKG, "libmdc_pngw.so")
+LIB_PNGW_RGB_PATH = os.path.join(_PKG, "libmdc_pngw_rgb.so")
 LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
 _hip = None
 _host = None
@@ -334,6 +347,7 @@ _bench = None
 _jenc = None
 _zipw = None
 _pngw = None
+_pngw_rgb = None
 _pngd = None
 
 
@@ -406,6 +420,15 @@ def pngw_lib():
         _share_hip_runtime_with_torch()
         _pngw = _load(LIB_PNGW_PATH, PNGW_API)
     return _pngw
+
+
+def pngw_rgb_lib():
+    """libmdc_pngw_rgb.so: the PNG encoder for device-resident 8-bit RGB images (include/mdc_pngw_rgb.h)."""
+    global _pngw_rgb
+    if _pngw_rgb is None:
+        _share_hip_runtime_with_torch()
+        _pngw_rgb = _load(LIB_PNGW_RGB_PATH, PNGW_RGB_API)
+    return _pngw_rgb
 
 
 def pngd_lib():
@@ -913,6 +936,46 @@ class Context:
                "iters": [{k: getattr(its[i], k) for k in names} for i in range(int(iterations))]}
         return G, E, log
 
+    def rcal_plot_e(self, d_E, w, h, stream=0):
+        """plotE (:72-119) of d_E (w*h float64) -> (rgb (h, w, 3) uint8 in file order R, G, B, e16 (h, w) uint16 (held as int16 bits),
+        (Emin, Emax)); synchronises."""
+        import torch
+
+        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=d_E.device)
+        e16 = torch.empty((h, w), dtype=torch.int16, device=d_E.device)
+        rng = (C.c_double * 2)()
+        self._chk(self._L.mdc_rcal_plot_e_device(self._h, d_E.data_ptr(), int(w), int(h), rgb.data_ptr(), e16.data_ptr(), rng, _stream(stream)))
+        return rgb, e16, (rng[0], rng[1])
+
+    def rcal_plot_g(self, d_G, stream=0):
+        """plotG (:120-146) of d_G (256 float64) -> (img (256, 256) float32 = GImg * 255, (min, max)); synchronises."""
+        import torch
+
+        img = torch.empty((256, 256), dtype=torch.float32, device=d_G.device)
+        rng = (C.c_double * 2)()
+        self._chk(self._L.mdc_rcal_plot_g_device(self._h, d_G.data_ptr(), img.data_ptr(), rng, _stream(stream)))
+        return img, (rng[0], rng[1])
+
+    def vcal_plot_plane(self, d_plane, gw, gh, stream=0):
+        """displayImage (src/main_vignetteCalib.cpp:72-94) of the gw x gh plane colours (float32) -> (rgb (gh, gw, 3) uint8 in file
+        order, (vmin, vmax) as floats); synchronises."""
+        import torch
+
+        rgb = torch.empty((gh, gw, 3), dtype=torch.uint8, device=d_plane.device)
+        rng = (C.c_float * 2)()
+        self._chk(self._L.mdc_vcal_plot_plane_device(self._h, d_plane.data_ptr(), int(gw), int(gh), rgb.data_ptr(), rng, _stream(stream)))
+        return rgb, (rng[0], rng[1])
+
+    def vcal_vignette_u16(self, d_vignette, d_out=None, stream=0):
+        """The 16-bit pixels of vignette.png / vignetteSmoothed.png (:568-583) of a float32 map -> uint16 values in an int16 tensor of
+        the same shape (d_out if given); synchronises."""
+        import torch
+
+        if d_out is None:
+            d_out = torch.empty(d_vignette.shape, dtype=torch.int16, device=d_vignette.device)
+        self._chk(self._L.mdc_vcal_vignette_u16_device(self._h, d_vignette.data_ptr(), d_vignette.numel(), d_out.data_ptr(), _stream(stream)))
+        return d_out
+
     def bind(self, fov=None, photo=None):
         rc = host_lib().mdch_bind(self._h, fov._h if fov is not None else None, photo._h if photo is not None else None)
         self._chk(rc)
@@ -1138,27 +1201,35 @@ PNG_FILTER_ADAPTIVE = 5  # MDCP_FILTER_ADAPTIVE
 
 
 class PngEncoder:
-    """One mdcp_encoder (include/mdc_pngw.h): device-resident w x h grayscale images of `depth` bits -> one PNG file per image
-    (filtered, Huffman-only DEFLATE with a stored fallback).  encode() fills device slots (the encoder's own unless d_out /
-    d_sizes are given) in the layout ZipWriter.append() takes and returns their device addresses; it does not synchronise."""
+    """One mdcp_encoder: device-resident w x h grayscale images of `depth` bits (include/mdc_pngw.h) or, with rgb=True, 8-bit RGB
+    images of three bytes R, G, B per pixel (include/mdc_pngw_rgb.h, a library of its own; `depth` is then ignored) -> one PNG
+    file per image (filtered, Huffman-only DEFLATE with a stored fallback).  encode() fills device slots (the encoder's own unless
+    d_out / d_sizes are given) in the layout ZipWriter.append() takes and returns their device addresses; it does not synchronise."""
 
-    def __init__(self, w, h, depth=8, filter=PNG_FILTER_ADAPTIVE, max_images=1, device=-1):
-        self._L = pngw_lib()
-        self.w, self.h, self.depth, self.filter, self.max_images = int(w), int(h), int(depth), int(filter), int(max_images)
+    def __init__(self, w, h, depth=8, filter=PNG_FILTER_ADAPTIVE, max_images=1, device=-1, rgb=False):
+        self.rgb = bool(rgb)
+        self._L = pngw_rgb_lib() if self.rgb else pngw_lib()
+        L = self._L
+        self._last_error, self._destroy, self._output = ((L.mdcp_last_error_rgb8, L.mdcp_destroy_rgb8, L.mdcp_output_device_rgb8) if self.rgb else
+                                                         (L.mdcp_last_error, L.mdcp_destroy, L.mdcp_output_device))
+        self.w, self.h, self.depth, self.filter, self.max_images = int(w), int(h), 8 if self.rgb else int(depth), int(filter), int(max_images)
         h_ = _vp()
-        self._check(self._L.mdcp_create(int(device), self.w, self.h, self.depth, self.filter, self.max_images, C.byref(h_)))
+        if self.rgb:
+            self._check(L.mdcp_create_rgb8(int(device), self.w, self.h, self.filter, self.max_images, C.byref(h_)))
+        else:
+            self._check(L.mdcp_create(int(device), self.w, self.h, self.depth, self.filter, self.max_images, C.byref(h_)))
         self._h = h_
-        self.bound = int(self._L.mdcp_png_bound(self.w, self.h, self.depth))
+        self.bound = int(L.mdcp_png_bound_rgb8(self.w, self.h) if self.rgb else L.mdcp_png_bound(self.w, self.h, self.depth))
         self._own = None
 
     def _check(self, rc):
         if rc < 0:
-            raise MdcError(int(rc), self._L.mdcp_last_error().decode())
+            raise MdcError(int(rc), self._last_error().decode())
         return rc
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.mdcp_destroy(self._h)
+            self._destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -1167,17 +1238,22 @@ class PngEncoder:
         """(d_out, slot_bytes, d_sizes): the encoder's own output arrays, max_images slots of `bound` bytes"""
         if self._own is None:
             o, n, z = _vp(), _i64(), _vp()
-            self._check(self._L.mdcp_output_device(self._h, C.byref(o), C.byref(n), C.byref(z)))
+            self._check(self._output(self._h, C.byref(o), C.byref(n), C.byref(z)))
             self._own = (o.value, n.value, z.value)
         return self._own
 
-    def encode(self, d_images, nimages, kind="u8", stride=None, d_out=None, slot_bytes=None, d_sizes=None, stream=0):
-        """d_images: device address of nimages images of `kind` ("u8", "u16" or "f32"), stride elements apart (default w * h).
+    def encode(self, d_images, nimages, kind=None, stride=None, d_out=None, slot_bytes=None, d_sizes=None, stream=0):
+        """d_images: device address of nimages images of `kind` ("u8" (the default), "u16" or "f32"; "rgb8", the only kind and the
+        default of an RGB encoder), stride elements apart (default w * h; "rgb8": stride bytes apart, default 3 * w * h).
         -> (d_out, slot_bytes, d_sizes), device addresses."""
+        kind = kind or ("rgb8" if self.rgb else "u8")
+        if (kind == "rgb8") != self.rgb:
+            raise MdcError(ERR_ARG, "PngEncoder.encode: kind %r on %s encoder" % (kind, "an RGB" if self.rgb else "a gray"))
         if d_out is None:
             d_out, slot_bytes, d_sizes = self.output()
-        fn = {"u8": self._L.mdcp_encode_u8_device, "u16": self._L.mdcp_encode_u16_device, "f32": self._L.mdcp_encode_f32_device}[kind]
-        self._check(fn(self._h, d_images, self.w * self.h if stride is None else int(stride), int(nimages), d_out, int(slot_bytes), d_sizes, _stream(stream)))
+        fn = getattr(self._L, "mdcp_encode_%s_device" % kind)
+        dense = self.w * self.h * (3 if self.rgb else 1)
+        self._check(fn(self._h, d_images, dense if stride is None else int(stride), int(nimages), d_out, int(slot_bytes), d_sizes, _stream(stream)))
         return d_out, int(slot_bytes), d_sizes
 
 

@@ -956,6 +956,26 @@ int mdc_vcal_smooth_device(mdc_ctx* c, const float* d_vignette_factor, int w, in
   return MDC_OK;
 } MDC_CATCH(c)
 
+int mdc_vcal_plot_plane_device(mdc_ctx* c, const float* d_plane, int gw, int gh, uint8_t* d_rgb, float* range_host, void* stream) try {
+  if (!c) return mdc_device_count() > 0 ? MDC_ERR_ARG : MDC_ERR_NO_DEVICE;
+  if (!d_plane || !d_rgb || !range_host || gw < 1 || gh < 1 || (long long)gw * gh >= (1ll << 31))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_plot_plane_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_plot_plane(d_plane, (long long)gw * gh, d_rgb, range_host, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_vignette_u16_device(mdc_ctx* c, const float* d_vignette, int64_t n, uint16_t* d_out, void* stream) try {
+  if (!c) return mdc_device_count() > 0 ? MDC_ERR_ARG : MDC_ERR_NO_DEVICE;
+  if (n < 0 || (n > 0 && (!d_vignette || !d_out)) || ((uintptr_t)d_out & 1) || ((uintptr_t)d_vignette & 3))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_vignette_u16_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_vignette_u16(d_vignette, n, d_out, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
 int mdc_vcal_solve_device(mdc_ctx* c, const float* d_images, const float* d_p2x, const float* d_p2y, int n_images, int w, int h,
                           int n_plane, float* d_plane_color, float* d_vignette_factor, int max_iterations, int outlier_th,
                           double* er_out, void* stream) try {

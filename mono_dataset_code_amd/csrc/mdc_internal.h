@@ -155,6 +155,10 @@ hipError_t launch_vcal_plane_coords(const float* d_corners, float* d_hk, int n, 
                                     const DistortModel* m, int wI, int hI, float* d_p2x, float* d_p2y, hipStream_t s);
 // vignetteCalib's output smoothing (:541-566): four NaN-aware 3 x 3 mean passes; d_tt = result, d_ct = scratch
 hipError_t launch_vcal_smooth(const float* d_vig, int wI, int hI, float* d_tt, float* d_ct, hipStream_t s);
+// vignetteCalib's result images: displayImage's colour picture of the plane (:72-94; range_host = vmin, vmax) and the 16-bit
+// quantisation of vignette.png / vignetteSmoothed.png (:568-583); both synchronise `s`
+hipError_t launch_vcal_plot_plane(const float* d_plane, long long n, uint8_t* d_rgb, float* range_host, hipStream_t s);
+hipError_t launch_vcal_vignette_u16(const float* d_vignette, int64_t n, uint16_t* d_out, hipStream_t s);
 
 // JPEG ingest, device half: coefficient records (per frame: 64 x u16 luma quantisation table, then blocks_rows x blocks_w blocks
 // of 64 quantised int16 coefficients, natural order; record_bytes apart) -> 8-bit frames (nframes * w * h), libjpeg's islow

@@ -1,5 +1,8 @@
 // libmdc_pngw.so (include/mdc_pngw.h): PNG files of device-resident grayscale images, made on the device.  One translation unit;
 // the only thing it takes from elsewhere is mdcz_crc32_device (libmdc_zipw.so) for the IDAT chunk's CRC.
+// Built with -DMDCP_RGB8_LIBRARY the same unit is libmdc_pngw_rgb.so (include/mdc_pngw_rgb.h) instead: the 8-bit RGB kind, whose pixel is
+// one 3-byte sample of the filter kernel, with entry points of its own and none of the gray ones -- so the gray library, its kernels
+// and its exported names are what they were, and the two can be loaded side by side.
 //
 // One call is six kernels and the checksum, with no host round trip between them:
 //   pngw_filter_kernel   16 rows per workgroup, one wave per row: the row's filter type (adaptive: all five sums first), the filtered
@@ -18,6 +21,9 @@
 //   pngw_finish_kernel   signature, IHDR, IDAT length and tag, zlib header, Adler-32, IEND, d_sizes[f]; then mdcz_crc32_device over
 //                        tag + data, and pngw_crc_kernel puts the four bytes in.
 #include "../../include/mdc_pngw.h"
+#ifdef MDCP_RGB8_LIBRARY
+#include "../../include/mdc_pngw_rgb.h"
+#endif
 
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -238,6 +244,10 @@ PNGW_HD void build_block(BuildLds& L, long long F) {
 
 __device__ __forceinline__ int sample_of(uint8_t v) { return v; }
 __device__ __forceinline__ int sample_of(uint16_t v) { return v; }
+struct Rgb8 {  // one pixel of an 8-bit RGB image in file order: the filter distance is the pixel, as it is the sample of a gray image
+  uint8_t r, g, b;
+};
+__device__ __forceinline__ int sample_of(Rgb8 v) { return ((int)v.r << 16) | ((int)v.g << 8) | (int)v.b; }
 __device__ __forceinline__ int sample_of(float v) {  // as mdcj_encode_f32_device: cv::Mat::convertTo(CV_8U)
   const float r = fminf(fmaxf(rintf(v), 0.0f), 255.0f);
   return v != v ? 0 : (int)r;
@@ -260,6 +270,13 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
   return v;
 }
 
+// image f of a batch: `stride` elements on, for RGB pixels `stride` bytes on (three-byte pixels, images at any byte distance)
+template <typename T>
+__device__ __forceinline__ const T* image_at(const T* images, long long f, long long stride) { return images + f * stride; }
+__device__ __forceinline__ const Rgb8* image_at(const Rgb8* images, long long f, long long stride) {
+  return (const Rgb8*)((const uint8_t*)images + f * stride);
+}
+
 template <typename T, int BPP>
 __global__ __launch_bounds__(256) void pngw_filter_kernel(const T* __restrict__ images, long long stride, long long nimages, int w, int h, int filter,
                                                           uint8_t* __restrict__ filt, long long filt_stride, uint32_t* __restrict__ zeroed) {
@@ -274,7 +291,7 @@ __global__ __launch_bounds__(256) void pngw_filter_kernel(const T* __restrict__ 
     const int y1 = y0 + kRowsPerGroup < h ? y0 + kRowsPerGroup : h;
     for (int i = t; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0;
     __syncthreads();
-    const T* __restrict__ img = images + f * stride;
+    const T* __restrict__ img = image_at(images, f, stride);
     uint8_t* __restrict__ out = filt + f * filt_stride;
     unsigned long long s1 = 0, s2 = 0;
     for (int y = y0 + wave; y < y1; y += 4) {
@@ -614,12 +631,24 @@ void put_be32(uint8_t* p, uint32_t v) {
   p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
 }
 
+// the stored form's size for rows of 1 + w * bpp bytes; -1 past 2^31 - 1
+int64_t bound_of(int w, int h, int bpp) {
+  if (w < 1 || h < 1) return -1;
+  const int64_t row = 1 + (int64_t)w * bpp;  // < 2^33
+  if (row > INT32_MAX / (int64_t)h) return -1;
+  const int64_t bound = 57 + 6 + stored_bytes(row * h);
+  return bound > INT32_MAX ? -1 : bound;
+}
+
+int create(const char* who, int device, int w, int h, int depth, int filter, int max_images, mdcp_encoder** out);
+void destroy(mdcp_encoder* enc);
+
 int grid_for(long long items) { return (int)(items < 1 ? 1 : items > kMaxGrid ? kMaxGrid : items); }
 
 }  // namespace
 
 struct mdcp_encoder {
-  int device = -1, w = 0, h = 0, depth = 0, filter = 0, max_images = 0;
+  int device = -1, w = 0, h = 0, depth = 0, filter = 0, max_images = 0;  // depth: bits per pixel -- 8, 16, or 24 for 8-bit RGB
   long long F = 0, nunits = 0;
   uint8_t* d_head = nullptr;
   uint8_t* d_filt = nullptr;
@@ -632,19 +661,9 @@ struct mdcp_encoder {
   int32_t* d_sizes = nullptr;
 };
 
-extern "C" {
+namespace {
 
-int64_t mdcp_png_bound(int w, int h, int depth) {
-  if (w < 1 || h < 1 || (depth != 8 && depth != 16)) return -1;
-  const int64_t row = 1 + (int64_t)w * (depth / 8);  // < 2^33
-  if (row > INT32_MAX / (int64_t)h) return -1;
-  const int64_t bound = 57 + 6 + stored_bytes(row * h);
-  return bound > INT32_MAX ? -1 : bound;
-}
-
-const char* mdcp_last_error(void) { return g_error; }
-
-void mdcp_destroy(mdcp_encoder* enc) {
+void destroy(mdcp_encoder* enc) {
   if (!enc) return;
   {
     DeviceGuard dg(enc->device);
@@ -661,25 +680,23 @@ void mdcp_destroy(mdcp_encoder* enc) {
   delete enc;
 }
 
-int mdcp_create(int device, int w, int h, int depth, int filter, int max_images, mdcp_encoder** out) {
-  if (!out) return fail(MDCP_ERR_ARG, "mdcp_create: out is null");
-  *out = nullptr;
-  if (depth != 8 && depth != 16) return fail(MDCP_ERR_ARG, "mdcp_create: depth %d is neither 8 nor 16", depth);
-  if (filter < 0 || filter > MDCP_FILTER_ADAPTIVE) return fail(MDCP_ERR_ARG, "mdcp_create: filter %d is outside 0..%d", filter, MDCP_FILTER_ADAPTIVE);
-  if (max_images < 1) return fail(MDCP_ERR_ARG, "mdcp_create: max_images %d is below 1", max_images);
-  if (w < 1 || h < 1) return fail(MDCP_ERR_SIZE, "mdcp_create: %d x %d: width and height start at 1", w, h);
-  if (mdcp_png_bound(w, h, depth) < 0) return fail(MDCP_ERR_SIZE, "mdcp_create: a %d x %d image of %d bits passes 2^31 - 1 bytes (sizes are int32_t)", w, h, depth);
+// depth = bits per pixel: 8 or 16 (gray), 24 (8-bit RGB)
+int create(const char* who, int device, int w, int h, int depth, int filter, int max_images, mdcp_encoder** out) {
+  if (filter < 0 || filter > MDCP_FILTER_ADAPTIVE) return fail(MDCP_ERR_ARG, "%s: filter %d is outside 0..%d", who, filter, MDCP_FILTER_ADAPTIVE);
+  if (max_images < 1) return fail(MDCP_ERR_ARG, "%s: max_images %d is below 1", who, max_images);
+  if (w < 1 || h < 1) return fail(MDCP_ERR_SIZE, "%s: %d x %d: width and height start at 1", who, w, h);
+  if (bound_of(w, h, depth / 8) < 0) return fail(MDCP_ERR_SIZE, "%s: a %d x %d image of %d bits passes 2^31 - 1 bytes (sizes are int32_t)", who, w, h, depth);
   const long long F = (1 + (long long)w * (depth / 8)) * h, nunits = (F + 15) / 16;
   const long long per_image = 24 * nunits + kSmallBytes;
   if (per_image > (1ll << 40) / max_images)
-    return fail(MDCP_ERR_SIZE, "mdcp_create: %d images x %lld bytes of scratch pass 2^40 bytes", max_images, per_image);
+    return fail(MDCP_ERR_SIZE, "%s: %d images x %lld bytes of scratch pass 2^40 bytes", who, max_images, per_image);
   int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MDCP_ERR_NO_DEVICE, "mdcp_create: no HIP device");
-  if (device >= count) return fail(MDCP_ERR_NO_DEVICE, "mdcp_create: device %d of %d", device, count);
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(MDCP_ERR_HIP, "mdcp_create: hipGetDevice failed");
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MDCP_ERR_NO_DEVICE, "%s: no HIP device", who);
+  if (device >= count) return fail(MDCP_ERR_NO_DEVICE, "%s: device %d of %d", who, device, count);
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(MDCP_ERR_HIP, "%s: hipGetDevice failed", who);
   DeviceGuard dg(device);
   mdcp_encoder* e = new (std::nothrow) mdcp_encoder;
-  if (!e) return fail(MDCP_ERR_NOMEM, "mdcp_create: out of host memory");
+  if (!e) return fail(MDCP_ERR_NOMEM, "%s: out of host memory", who);
   e->device = device, e->w = w, e->h = h, e->depth = depth, e->filter = filter, e->max_images = max_images;
   e->F = F, e->nunits = nunits;
   const size_t n = (size_t)max_images;
@@ -688,38 +705,40 @@ int mdcp_create(int device, int w, int h, int depth, int filter, int max_images,
       hipMalloc((void**)&e->d_tab, n * kTabWords * 4) != hipSuccess || hipMalloc((void**)&e->d_crc_len, n * 4) != hipSuccess ||
       hipMalloc((void**)&e->d_crc, n * 4) != hipSuccess) {
     (void)hipGetLastError();
-    mdcp_destroy(e);
-    return fail(MDCP_ERR_NOMEM, "mdcp_create: could not allocate the scratch arrays of %d images of %d x %d", max_images, w, h);
+    destroy(e);
+    return fail(MDCP_ERR_NOMEM, "%s: could not allocate the scratch arrays of %d images of %d x %d", who, max_images, w, h);
   }
   uint8_t head[48] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n', 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
   put_be32(head + 16, (uint32_t)w);
   put_be32(head + 20, (uint32_t)h);
-  head[24] = (uint8_t)depth;  // colour type, compression, filter method, interlace: 0
+  head[24] = (uint8_t)(depth == 24 ? 8 : depth);
+  head[25] = depth == 24 ? 2 : 0;  // colour type: truecolour or gray; compression, filter method, interlace: 0
   put_be32(head + 29, crc32_host(head + 12, 17));
   const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
   memcpy(head + 33, iend, 12);
   if (hipMemcpy(e->d_head, head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) {
-    mdcp_destroy(e);
-    return fail(MDCP_ERR_HIP, "mdcp_create: copying the header failed");
+    destroy(e);
+    return fail(MDCP_ERR_HIP, "%s: copying the header failed", who);
   }
   *out = e;
   return MDCP_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
 template <typename T, int BPP>
 int encode(const char* who, mdcp_encoder* e, const T* d_images, int64_t stride, int nimages, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes, void* stream) {
+  constexpr int kPerElement = BPP == 3 ? 3 : 1;      // an RGB stride is given in bytes, a gray one in elements
+  constexpr size_t kAlign = BPP == 3 ? 1 : sizeof(T);  // RGB pixels are bytes
   if (!e) return fail(MDCP_ERR_ARG, "%s: encoder is null", who);
   if (e->depth != 8 * BPP) return fail(MDCP_ERR_ARG, "%s: the encoder was made for %d-bit images", who, e->depth);
   if (nimages < 0 || nimages > e->max_images) return fail(MDCP_ERR_ARG, "%s: %d images, the encoder was made for 0..%d", who, nimages, e->max_images);
   if (nimages == 0) return MDCP_OK;
   if (!d_images || !d_out || !d_sizes) return fail(MDCP_ERR_ARG, "%s: null device pointer", who);
-  if ((uintptr_t)d_images % sizeof(T)) return fail(MDCP_ERR_ARG, "%s: d_images %p is not aligned to its %zu-byte elements", who, (const void*)d_images, sizeof(T));
-  if (stride < (int64_t)e->w * e->h) return fail(MDCP_ERR_ARG, "%s: stride %lld is below %d x %d", who, (long long)stride, e->w, e->h);
-  const int64_t bound = mdcp_png_bound(e->w, e->h, e->depth);
+  if ((uintptr_t)d_images % kAlign) return fail(MDCP_ERR_ARG, "%s: d_images %p is not aligned to its %zu-byte elements", who, (const void*)d_images, sizeof(T));
+  if (stride < (int64_t)e->w * e->h * kPerElement)
+    return fail(MDCP_ERR_ARG, "%s: stride %lld is below %d x %d%s", who, (long long)stride, e->w, e->h, kPerElement == 3 ? " x 3 bytes" : "");
+  const int64_t bound = bound_of(e->w, e->h, BPP);
+  if (slot_bytes < bound && BPP == 3)
+    return fail(MDCP_ERR_SIZE, "%s: slot_bytes %lld is below mdcp_png_bound_rgb8(%d, %d) = %lld", who, (long long)slot_bytes, e->w, e->h, (long long)bound);
   if (slot_bytes < bound)
     return fail(MDCP_ERR_SIZE, "%s: slot_bytes %lld is below mdcp_png_bound(%d, %d, %d) = %lld", who, (long long)slot_bytes, e->w, e->h, e->depth, (long long)bound);
   DeviceGuard dg(e->device);
@@ -746,9 +765,68 @@ int encode(const char* who, mdcp_encoder* e, const T* d_images, int64_t stride, 
   return MDCP_OK;
 }
 
+int output_device(const char* who, mdcp_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
+  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(MDCP_ERR_ARG, "%s: null argument", who);
+  const int64_t bound = bound_of(enc->w, enc->h, enc->depth / 8);
+  if (!enc->d_out) {
+    DeviceGuard dg(enc->device);
+    uint8_t* o = nullptr;
+    int32_t* z = nullptr;
+    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_images) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_images * sizeof(int32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(o);
+      return fail(MDCP_ERR_NOMEM, "%s: could not allocate %d slots of %lld bytes", who, enc->max_images, (long long)bound);
+    }
+    enc->d_out = o, enc->d_sizes = z;
+  }
+  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
+  return MDCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+#ifdef MDCP_RGB8_LIBRARY
+
+int64_t mdcp_png_bound_rgb8(int w, int h) { return bound_of(w, h, 3); }
+
+const char* mdcp_last_error_rgb8(void) { return g_error; }
+
+int mdcp_create_rgb8(int device, int w, int h, int filter, int max_images, mdcp_encoder** out) {
+  if (!out) return fail(MDCP_ERR_ARG, "mdcp_create_rgb8: out is null");
+  *out = nullptr;
+  return create("mdcp_create_rgb8", device, w, h, 24, filter, max_images, out);
+}
+
+void mdcp_destroy_rgb8(mdcp_encoder* enc) { destroy(enc); }
+
+int mdcp_encode_rgb8_device(mdcp_encoder* enc, const uint8_t* d_images, int64_t stride_bytes, int nimages, uint8_t* d_out, int64_t slot_bytes,
+                            int32_t* d_sizes, void* stream) {
+  return encode<Rgb8, 3>("mdcp_encode_rgb8_device", enc, (const Rgb8*)d_images, stride_bytes, nimages, d_out, slot_bytes, d_sizes, stream);
+}
+
+int mdcp_output_device_rgb8(mdcp_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
+  return output_device("mdcp_output_device_rgb8", enc, d_out, slot_bytes, d_sizes);
+}
+
+#else
+
+int64_t mdcp_png_bound(int w, int h, int depth) {
+  if (depth != 8 && depth != 16) return -1;
+  return bound_of(w, h, depth / 8);
+}
+
+const char* mdcp_last_error(void) { return g_error; }
+
+int mdcp_create(int device, int w, int h, int depth, int filter, int max_images, mdcp_encoder** out) {
+  if (!out) return fail(MDCP_ERR_ARG, "mdcp_create: out is null");
+  *out = nullptr;
+  if (depth != 8 && depth != 16) return fail(MDCP_ERR_ARG, "mdcp_create: depth %d is neither 8 nor 16", depth);
+  return create("mdcp_create", device, w, h, depth, filter, max_images, out);
+}
+
+void mdcp_destroy(mdcp_encoder* enc) { destroy(enc); }
 
 int mdcp_encode_u8_device(mdcp_encoder* enc, const uint8_t* d_images, int64_t stride, int nimages, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes,
                           void* stream) {
@@ -766,21 +844,7 @@ int mdcp_encode_f32_device(mdcp_encoder* enc, const float* d_images, int64_t str
 }
 
 int mdcp_output_device(mdcp_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
-  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(MDCP_ERR_ARG, "mdcp_output_device: null argument");
-  const int64_t bound = mdcp_png_bound(enc->w, enc->h, enc->depth);
-  if (!enc->d_out) {
-    DeviceGuard dg(enc->device);
-    uint8_t* o = nullptr;
-    int32_t* z = nullptr;
-    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_images) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_images * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(o);
-      return fail(MDCP_ERR_NOMEM, "mdcp_output_device: could not allocate %d slots of %lld bytes", enc->max_images, (long long)bound);
-    }
-    enc->d_out = o, enc->d_sizes = z;
-  }
-  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
-  return MDCP_OK;
+  return output_device("mdcp_output_device", enc, d_out, slot_bytes, d_sizes);
 }
 
 int mdcp_huffman_lengths_device(const uint32_t* d_hist, int nsym, int limit, uint8_t* d_lengths, void* stream) {
@@ -794,5 +858,7 @@ int mdcp_huffman_lengths_device(const uint32_t* d_hist, int nsym, int limit, uin
   if (err != hipSuccess) return fail(MDCP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
   return MDCP_OK;
 }
+
+#endif  // MDCP_RGB8_LIBRARY
 
 }  // extern "C"

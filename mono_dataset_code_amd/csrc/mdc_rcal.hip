@@ -16,7 +16,11 @@
 //   rmse                    : per lane double partials over at most 4 x n terms, then double-double in a fixed tree and a
 //                             fixed slab order; the count is an exact integer.
 // No float atomics anywhere.
+//
+// The result images (plotE / plotG, :72-146) are rendered at the end of this file: a (value, index) min/max reduction
+// (minmax_first.h) and one lane per pixel that evaluates the reference's expression in its order.
 #include "mdc_ctx.h"
+#include "minmax_first.h"
 
 namespace mdc {
 namespace {
@@ -671,6 +675,114 @@ static hipError_t rescale(const uint8_t* d_images, const double* d_t, int n, uns
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------- plotE / plotG (:72-146)
+
+constexpr int kPlotBlocks = 256;  // one pass of the range kernel's grid covers kPlotBlocks * kRcalThreads = 65536 pixels
+
+// part[b] = workgroup b's range of le = log(E + 20), part[gridDim.x + b] = its range of E
+__global__ __launch_bounds__(kRcalThreads) void rcal_plot_e_range_kernel(const double* __restrict__ E, long long n, MinMaxFirst<double>* __restrict__ part) {
+  __shared__ MinMaxFirst<double> s_m[kRcalThreads];
+  MinMaxFirst<double> le = mm_start<double>(), e = mm_start<double>();
+  for (long long i = (long long)blockIdx.x * kRcalThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kRcalThreads) {
+    const double v = E[i];
+    mm_take(le, log(v + 20.0), i);
+    mm_take(e, v, i);
+  }
+  le = mm_block<double, kRcalThreads>(le, s_m);
+  e = mm_block<double, kRcalThreads>(e, s_m);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = le;
+    part[gridDim.x + blockIdx.x] = e;
+  }
+}
+
+// workgroup q: range[2q], range[2q + 1] = the minimum and maximum over part[q * nparts .. (q + 1) * nparts)
+__global__ __launch_bounds__(kRcalThreads) void rcal_plot_range_final_kernel(const MinMaxFirst<double>* __restrict__ part, int nparts, double* __restrict__ range) {
+  __shared__ MinMaxFirst<double> s_m[kRcalThreads];
+  MinMaxFirst<double> m = mm_start<double>();
+  for (int i = threadIdx.x; i < nparts; i += kRcalThreads) {
+    const MinMaxFirst<double> o = part[(long long)blockIdx.x * nparts + i];
+    mm_take_lo(m, o.lo, o.ilo);
+    mm_take_hi(m, o.hi, o.ihi);
+  }
+  m = mm_block<double, kRcalThreads>(m, s_m);
+  if (threadIdx.x == 0) {
+    range[2 * blockIdx.x] = m.lo;
+    range[2 * blockIdx.x + 1] = m.hi;
+  }
+}
+
+// range = {min, max of le, Emin, Emax}; rgb in file order (the reference's Vec3b is B, G, R)
+__global__ __launch_bounds__(kRcalThreads) void rcal_plot_e_kernel(const double* __restrict__ E, long long n, const double* __restrict__ range,
+                                                                   uint8_t* __restrict__ rgb, uint16_t* __restrict__ e16) {
+  const double lmin = range[0], lmax = range[1], emin = range[2], emax = range[3];
+  for (long long i = (long long)blockIdx.x * kRcalThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kRcalThreads) {
+    const double v = E[i];
+    const float val = (float)(3 * (exp((log(v + 20.0) - lmin) / (lmax - lmin)) - 1) / 1.7183);  // :96
+    int icP = x86_int(val);
+    const float ifP = val - (float)icP;
+    icP = icP % 3;
+    const uint8_t c = (uint8_t)x86_int(255 * ifP);
+    uint8_t r = 0, g = 0, b = 0;  // cv::Vec3b() is zeros: no branch fires for a NaN or a negative val
+    if (icP == 0) r = c;
+    if (icP == 1) r = 255, g = c;
+    if (icP == 2) r = 255, g = 255, b = c;
+    rgb[3 * i] = r;
+    rgb[3 * i + 1] = g;
+    rgb[3 * i + 2] = b;
+    e16[i] = (uint16_t)x86_int(255 * 255 * (v - emin) / (emax - emin));  // :108
+  }
+}
+
+// one workgroup, lane i = column i of the 256 x 256 image: GImg * 255 as cv::imwrite receives it (:120-145)
+__global__ __launch_bounds__(256) void rcal_plot_g_kernel(const double* __restrict__ G, float* __restrict__ img, double* __restrict__ range) {
+  __shared__ MinMaxFirst<double> s_m[256];
+  const int i = threadIdx.x;
+  const double g = G[i];
+  MinMaxFirst<double> m = mm_start<double>();
+  mm_take(m, g, (long long)i);
+  m = mm_block<double, 256>(m, s_m);
+  if (i == 0) range[0] = m.lo, range[1] = m.hi;
+  const double val = 256 * (g - m.lo) / (m.hi - m.lo);
+  for (int k = 0; k < 256; k++) img[k * 256 + i] = val < k ? (float)(k - val) * 255.0f : 0.0f;
+}
+
+static hipError_t plot_e(const double* d_E, long long n, uint8_t* d_rgb, uint16_t* d_e16, double* range_host, hipStream_t s) {
+  const int blocks = (int)std::min<long long>(kPlotBlocks, (n + kRcalThreads - 1) / kRcalThreads);
+  MinMaxFirst<double>* d_part = nullptr;
+  double* d_range = nullptr;
+  hipError_t e = hipMalloc(&d_part, 2 * (size_t)blocks * sizeof(MinMaxFirst<double>));
+  if (e == hipSuccess) e = hipMalloc(&d_range, 4 * sizeof(double));
+  double range[4] = {0, 0, 0, 0};
+  if (e == hipSuccess) {
+    rcal_plot_e_range_kernel<<<blocks, kRcalThreads, 0, s>>>(d_E, n, d_part);
+    rcal_plot_range_final_kernel<<<2, kRcalThreads, 0, s>>>(d_part, blocks, d_range);
+    rcal_plot_e_kernel<<<(int)std::min<long long>(4096, (n + kRcalThreads - 1) / kRcalThreads), kRcalThreads, 0, s>>>(d_E, n, d_range, d_rgb, d_e16);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(range, d_range, sizeof range, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // the scratch is freed below
+  (void)hipFree(d_part);
+  (void)hipFree(d_range);
+  if (e == hipSuccess && e2 == hipSuccess) range_host[0] = range[2], range_host[1] = range[3];
+  return e != hipSuccess ? e : e2;
+}
+
+static hipError_t plot_g(const double* d_G, float* d_img, double* range_host, hipStream_t s) {
+  double* d_range = nullptr;
+  hipError_t e = hipMalloc(&d_range, 2 * sizeof(double));
+  double range[2] = {0, 0};
+  if (e == hipSuccess) {
+    rcal_plot_g_kernel<<<1, 256, 0, s>>>(d_G, d_img, d_range);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(range, d_range, sizeof range, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)hipFree(d_range);
+  if (e == hipSuccess && e2 == hipSuccess) range_host[0] = range[0], range_host[1] = range[1];
+  return e != hipSuccess ? e : e2;
+}
+
 }  // namespace mdc
 
 using namespace mdc;
@@ -815,6 +927,25 @@ int mdc_rcal_rescale_device(mdc_ctx* c, const uint8_t* d_images, const double* d
   MDC_HIP(c, wk.alloc((unsigned)w * h, false));
   MDC_HIP(c, rescale(d_images, d_exposure, n_images, (unsigned)w * h, d_G, d_E, wk, d_rmse_e, d_rmse_resc, s));
   MDC_HIP(c, hipStreamSynchronize(s));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_rcal_plot_e_device(mdc_ctx* c, const double* d_E, int w, int h, uint8_t* d_rgb, uint16_t* d_e16, double* range_host, void* stream) try {
+  if (!c) return no_ctx();
+  if (!d_E || !d_rgb || !d_e16 || !range_host || w < 1 || h < 1 || (long long)w * h >= (1ll << 31) || ((uintptr_t)d_e16 & 1))
+    return fail(c, MDC_ERR_ARG, "mdc_rcal_plot_e_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, plot_e(d_E, (long long)w * h, d_rgb, d_e16, range_host, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_rcal_plot_g_device(mdc_ctx* c, const double* d_G, float* d_img, double* range_host, void* stream) try {
+  if (!c) return no_ctx();
+  if (!d_G || !d_img || !range_host) return fail(c, MDC_ERR_ARG, "mdc_rcal_plot_g_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, plot_g(d_G, d_img, range_host, (hipStream_t)stream));
   return MDC_OK;
 } MDC_CATCH(c)
 

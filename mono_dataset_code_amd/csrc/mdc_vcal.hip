@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mdc_internal.h"
+#include "minmax_first.h"
 
 namespace mdc {
 namespace {
@@ -616,7 +617,82 @@ __global__ __launch_bounds__(kGradThreads) void gradients_levels_kernel(GradLeve
 
 inline int blocks(long long n) { return (int)((n + 255) / 256); }
 
+// ---- the result images: displayImage (:72-94) and the 16-bit vignette files (:568-583)
+
+constexpr int kVcalPlotBlocks = 256;  // one pass of the range kernel's grid covers 256 * 256 = 65536 plane points
+
+__global__ __launch_bounds__(256) void vcal_plot_range_kernel(const float* __restrict__ I, long long n, MinMaxFirst<float>* __restrict__ part) {
+  __shared__ MinMaxFirst<float> s_m[256];
+  MinMaxFirst<float> m = mm_start<float>();
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) mm_take(m, I[i], i);
+  m = mm_block<float, 256>(m, s_m);
+  if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(256) void vcal_plot_range_final_kernel(const MinMaxFirst<float>* __restrict__ part, int nparts, float* __restrict__ range) {
+  __shared__ MinMaxFirst<float> s_m[256];
+  MinMaxFirst<float> m = mm_start<float>();
+  for (int i = threadIdx.x; i < nparts; i += 256) {
+    const MinMaxFirst<float> o = part[i];
+    mm_take_lo(m, o.lo, o.ilo);
+    mm_take_hi(m, o.hi, o.ihi);
+  }
+  m = mm_block<float, 256>(m, s_m);
+  if (threadIdx.x == 0) range[0] = m.lo, range[1] = m.hi;
+}
+
+// rgb in file order: the reference's NaN colour Vec3b(0, 0, 255) is B, G, R
+__global__ __launch_bounds__(256) void vcal_plot_plane_kernel(const float* __restrict__ I, long long n, const float* __restrict__ range, uint8_t* __restrict__ rgb) {
+  const float vmin = range[0], vmax = range[1];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float v = I[i];
+    const uint8_t c = (uint8_t)x86_int((255 * (v - vmin)) / (vmax - vmin));  // :88, float -> uchar as the Vec3b arguments convert
+    const bool nan = v != v;
+    rgb[3 * i] = nan ? 255 : c;
+    rgb[3 * i + 1] = nan ? 0 : c;
+    rgb[3 * i + 2] = nan ? 0 : c;
+  }
+}
+
+// cv::Mat(h, w, CV_32F, I) * 254.9 * 254.9 -> convertTo(CV_16U): one float scale, saturate_cast<ushort>(cvRound(v))
+__global__ __launch_bounds__(256) void vcal_vignette_u16_kernel(const float* __restrict__ I, long long n, uint16_t* __restrict__ out) {
+  const float scale = (float)(254.9 * 254.9);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float v = I[i] * scale;
+    const float r = fminf(fmaxf(rintf(v), 0.0f), 65535.0f);
+    out[i] = v != v ? (uint16_t)0 : (uint16_t)(int)r;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_vcal_plot_plane(const float* d_plane, long long n, uint8_t* d_rgb, float* range_host, hipStream_t s) {
+  const int nparts = (int)std::min<long long>(kVcalPlotBlocks, blocks(n));
+  MinMaxFirst<float>* d_part = nullptr;
+  float* d_range = nullptr;
+  hipError_t e = hipMalloc(&d_part, (size_t)nparts * sizeof(MinMaxFirst<float>));
+  if (e == hipSuccess) e = hipMalloc(&d_range, 2 * sizeof(float));
+  float range[2] = {0.f, 0.f};
+  if (e == hipSuccess) {
+    vcal_plot_range_kernel<<<nparts, 256, 0, s>>>(d_plane, n, d_part);
+    vcal_plot_range_final_kernel<<<1, 256, 0, s>>>(d_part, nparts, d_range);
+    vcal_plot_plane_kernel<<<(int)std::min<long long>(4096, blocks(n)), 256, 0, s>>>(d_plane, n, d_range, d_rgb);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(range, d_range, sizeof range, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // the scratch is freed below
+  (void)hipFree(d_part);
+  (void)hipFree(d_range);
+  if (e == hipSuccess && e2 == hipSuccess) range_host[0] = range[0], range_host[1] = range[1];
+  return e != hipSuccess ? e : e2;
+}
+
+hipError_t launch_vcal_vignette_u16(const float* d_vignette, int64_t n, uint16_t* d_out, hipStream_t s) {
+  if (n > 0) vcal_vignette_u16_kernel<<<(int)std::min<long long>(8192, (n + 255) / 256), 256, 0, s>>>(d_vignette, n, d_out);
+  const hipError_t e = hipGetLastError();
+  const hipError_t e2 = hipStreamSynchronize(s);
+  return e != hipSuccess ? e : e2;
+}
 
 hipError_t launch_gradients_levels(int n_levels, const float* const* d_src, float* const* d_dI, float* const* d_abs2, const int* w,
                                    const int* h, int64_t nframes, hipStream_t s) {
