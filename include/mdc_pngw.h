@@ -52,7 +52,8 @@
  *   (24 * ceil(F / 16) + 2792) bytes (the filtered bytes, a 64-bit bit offset per 16 of them, tables), at most 2^40 bytes;
  *   per call 0 <= nimages <= max_images, stride >= w * h elements, slot_bytes >= the bound, 16-bit images 2-byte aligned, float
  *   images 4-byte aligned; d_out and slot_bytes of any alignment.  Offsets across the batch are 64-bit.
- *   No LZ77: a smooth image is coded at its zeroth-order entropy, not below.  The code builder and the scan over an image's bit
+ *   No LZ77 in this library: a smooth image is coded at its zeroth-order entropy, not below -- unless it is encoded by
+ *   libmdc_pnglz.so (include/mdc_pnglz.h), which writes the same file with matches where they make it smaller.  The code builder and the scan over an image's bit
  *   offsets run in one workgroup per image: the encoder is made for batches of images, not for one large image.
  *
  * Threads: an encoder holds the scratch arrays of one call at a time -- calls on one encoder are ordered by the caller (same

@@ -206,13 +206,14 @@ def build_programs(force=False):
     """bin/responseCalib: the reference's responseCalib program on top of libmdc_host.so / libmdc_hip.so, and libmdc_pngw.so /
     libmdc_pngw_rgb.so for its result images;
     bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so;
-    bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those, libmdc_zipw.so
-    and libmdc_pngw.so."""
+    bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those, libmdc_zipw.so,
+    libmdc_pngw.so and libmdc_pnglz.so."""
     build_host(force)
     build_jenc(force)
     build_zipw(force)
     build_pngw(force)
     build_pngw_rgb(force)
+    build_pnglz(force)
     os.makedirs(BIN, exist_ok=True)
     deps = [RESPONSE_CALIB_SOURCE, LIB_HOST, LIB_HIP, LIB_PNGW, LIB_PNGW_RGB, LIB_ZIPW, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_pngw.h"),
             os.path.join(INC, "mdc_pngw_rgb.h"),
@@ -226,11 +227,11 @@ def build_programs(force=False):
     if force or _stale(PLAY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
               PLAY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-Wl,-rpath,$ORIGIN/..", "-o", PLAY_DATASET])
-    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_ZIPW, LIB_PNGW, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
-            os.path.join(INC, "mdc_zipw.h"), os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
+    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_ZIPW, LIB_PNGW, LIB_PNGLZ, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
+            os.path.join(INC, "mdc_zipw.h"), os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RECTIFY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
-              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_zipw", "-lmdc_pngw", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
+              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_zipw", "-lmdc_pngw", "-lmdc_pnglz", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
     return RESPONSE_CALIB
 
 
@@ -303,6 +304,31 @@ def build_pngw_rgb(force=False):
               "-Wall", "-DMDCP_RGB8_LIBRARY=1", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN",
               "-Wl,--version-script=" + PNGW_RGB_EXPORT_MAP, "-o", LIB_PNGW_RGB])
     return LIB_PNGW_RGB
+
+
+LIB_PNGLZ = os.path.join(PKG, "libmdc_pnglz.so")
+PNGLZ_SOURCE = os.path.join(CSRC, "mdc_pnglz.hip")
+PNGLZ_BLOCK = os.path.join(CSRC, "pnglz_block.h")
+PNGLZ_EXPORT_MAP = os.path.join(CSRC, "mdc_pnglz_exports.map")
+
+
+def build_pnglz(force=False):
+    """libmdc_pnglz.so: the device PNG encoder with LZ77 matches (include/mdc_pnglz.h), gray and RGB in one library -- one
+    translation unit plus the code builder it shares with the CPU test program, on top of libmdc_zipw.so; libmdc_pngw.so and
+    libmdc_pngw_rgb.so are not involved, and it is outside libmdc_hip.so's build identity."""
+    build_zipw(force)
+    if force or _stale(LIB_PNGLZ, [PNGLZ_SOURCE, PNGLZ_BLOCK, os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mdc_zipw.h"), PNGLZ_EXPORT_MAP, LIB_ZIPW]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, PNGLZ_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGLZ_EXPORT_MAP, "-o", LIB_PNGLZ])
+    return LIB_PNGLZ
+
+
+def build_pnglz_block_program(out, sanitize=True):
+    """tests/native/pnglz_block.cpp: csrc/pnglz_block.h (the code builder and header writer of libmdc_pnglz.so) as a stand-alone
+    program, under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_pnglz_cpu.py).  Pure host code."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pnglz_block.cpp"), "-o", out])
+    return out
 
 
 LIB_PNGD = os.path.join(PKG, "libmdc_pngd.so")
@@ -402,6 +428,7 @@ def build_all(force=False):
     build_zipw(force)
     build_pngw(force)
     build_pngw_rgb(force)
+    build_pnglz(force)
     build_pngd(force)
     build_debug()
     build_fault_injection()

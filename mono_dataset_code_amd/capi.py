@@ -321,6 +321,20 @@ PNGW_RGB_API = {  # include/mdc_pngw_rgb.h (libmdc_pngw_rgb.so: the same encoder
     "mdcp_encode_rgb8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
     "mdcp_output_device_rgb8": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
 }
+PNGLZ_API = {  # include/mdc_pnglz.h (libmdc_pnglz.so: the PNG encoder with LZ77 matches, gray and RGB, a library of its own)
+    "mdcl_png_bound": (_i64, [_i, _i, _i]),
+    "mdcl_last_error": (_cp, []),
+    "mdcl_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _P(_vp)]),
+    "mdcl_destroy": (None, [_vp]),
+    "mdcl_encode_u8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcl_encode_u16_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcl_encode_f32_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcl_encode_rgb8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcl_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
+    "mdcl_form_device": (_i, [_vp, _vp, _i, _vp]),
+    "mdcl_profile": (_i, [_vp, _i]),
+    "mdcl_kernel_ms": (_i, [_vp, _P(_f)]),
+}
 PNGD_API = {  # include/mdc_pngd.h (libmdc_pngd.so: the device PNG decoder, a library of its own)
     "mdci_last_error": (_cp, []),
     "mdci_scratch_bytes": (_i64, [_i, _i, _i]),
@@ -340,6 +354,7 @@ LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
 LIB_ZIPW_PATH = os.path.join(_PKG, "libmdc_zipw.so")
 LIB_PNGW_PATH = os.path.join(_PKG, "libmdc_pngw.so")
 LIB_PNGW_RGB_PATH = os.path.join(_PKG, "libmdc_pngw_rgb.so")
+LIB_PNGLZ_PATH = os.path.join(_PKG, "libmdc_pnglz.so")
 LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
 _hip = None
 _host = None
@@ -348,6 +363,7 @@ _jenc = None
 _zipw = None
 _pngw = None
 _pngw_rgb = None
+_pnglz = None
 _pngd = None
 
 
@@ -429,6 +445,15 @@ def pngw_rgb_lib():
         _share_hip_runtime_with_torch()
         _pngw_rgb = _load(LIB_PNGW_RGB_PATH, PNGW_RGB_API)
     return _pngw_rgb
+
+
+def pnglz_lib():
+    """libmdc_pnglz.so: the PNG encoder with LZ77 matches for device-resident gray and RGB images (include/mdc_pnglz.h)."""
+    global _pnglz
+    if _pnglz is None:
+        _share_hip_runtime_with_torch()
+        _pnglz = _load(LIB_PNGLZ_PATH, PNGLZ_API)
+    return _pnglz
 
 
 def pngd_lib():
@@ -1203,23 +1228,36 @@ PNG_FILTER_ADAPTIVE = 5  # MDCP_FILTER_ADAPTIVE
 class PngEncoder:
     """One mdcp_encoder: device-resident w x h grayscale images of `depth` bits (include/mdc_pngw.h) or, with rgb=True, 8-bit RGB
     images of three bytes R, G, B per pixel (include/mdc_pngw_rgb.h, a library of its own; `depth` is then ignored) -> one PNG
-    file per image (filtered, Huffman-only DEFLATE with a stored fallback).  encode() fills device slots (the encoder's own unless
-    d_out / d_sizes are given) in the layout ZipWriter.append() takes and returns their device addresses; it does not synchronise."""
+    file per image (filtered, Huffman-only DEFLATE with a stored fallback).  compress="lz77" takes libmdc_pnglz.so instead
+    (include/mdc_pnglz.h: the same files with LZ77 matches of depth `chain` where they make a file smaller; all three kinds).
+    encode() fills device slots (the encoder's own unless d_out / d_sizes are given) in the layout ZipWriter.append() takes and
+    returns their device addresses; it does not synchronise."""
 
-    def __init__(self, w, h, depth=8, filter=PNG_FILTER_ADAPTIVE, max_images=1, device=-1, rgb=False):
-        self.rgb = bool(rgb)
-        self._L = pngw_rgb_lib() if self.rgb else pngw_lib()
+    def __init__(self, w, h, depth=8, filter=PNG_FILTER_ADAPTIVE, max_images=1, device=-1, rgb=False, compress="huffman", chain=4):
+        if compress not in ("huffman", "lz77"):
+            raise MdcError(ERR_ARG, "PngEncoder: compress %r is neither 'huffman' nor 'lz77'" % (compress,))
+        self.rgb, self.lz77, self.chain = bool(rgb), compress == "lz77", int(chain)
+        self._L = pnglz_lib() if self.lz77 else pngw_rgb_lib() if self.rgb else pngw_lib()
         L = self._L
-        self._last_error, self._destroy, self._output = ((L.mdcp_last_error_rgb8, L.mdcp_destroy_rgb8, L.mdcp_output_device_rgb8) if self.rgb else
+        self._prefix = "mdcl_encode_%s_device" if self.lz77 else "mdcp_encode_%s_device"
+        self._last_error, self._destroy, self._output = ((L.mdcl_last_error, L.mdcl_destroy, L.mdcl_output_device) if self.lz77 else
+                                                         (L.mdcp_last_error_rgb8, L.mdcp_destroy_rgb8, L.mdcp_output_device_rgb8) if self.rgb else
                                                          (L.mdcp_last_error, L.mdcp_destroy, L.mdcp_output_device))
         self.w, self.h, self.depth, self.filter, self.max_images = int(w), int(h), 8 if self.rgb else int(depth), int(filter), int(max_images)
         h_ = _vp()
-        if self.rgb:
+        if self.lz77:
+            if not self.rgb and self.depth not in (8, 16):
+                raise MdcError(ERR_ARG, "PngEncoder: depth %d is neither 8 nor 16" % self.depth)
+            kind = 2 if self.rgb else 1 if self.depth == 16 else 0  # MDCL_RGB8, MDCL_GRAY16, MDCL_GRAY8
+            self._check(L.mdcl_create(int(device), self.w, self.h, kind, self.filter, self.chain, self.max_images, C.byref(h_)))
+            self.bound = int(L.mdcl_png_bound(self.w, self.h, kind))
+        elif self.rgb:
             self._check(L.mdcp_create_rgb8(int(device), self.w, self.h, self.filter, self.max_images, C.byref(h_)))
+            self.bound = int(L.mdcp_png_bound_rgb8(self.w, self.h))
         else:
             self._check(L.mdcp_create(int(device), self.w, self.h, self.depth, self.filter, self.max_images, C.byref(h_)))
+            self.bound = int(L.mdcp_png_bound(self.w, self.h, self.depth))
         self._h = h_
-        self.bound = int(L.mdcp_png_bound_rgb8(self.w, self.h) if self.rgb else L.mdcp_png_bound(self.w, self.h, self.depth))
         self._own = None
 
     def _check(self, rc):
@@ -1251,10 +1289,27 @@ class PngEncoder:
             raise MdcError(ERR_ARG, "PngEncoder.encode: kind %r on %s encoder" % (kind, "an RGB" if self.rgb else "a gray"))
         if d_out is None:
             d_out, slot_bytes, d_sizes = self.output()
-        fn = getattr(self._L, "mdcp_encode_%s_device" % kind)
+        fn = getattr(self._L, self._prefix % kind)
         dense = self.w * self.h * (3 if self.rgb else 1)
         self._check(fn(self._h, d_images, dense if stride is None else int(stride), int(nimages), d_out, int(slot_bytes), d_sizes, _stream(stream)))
         return d_out, int(slot_bytes), d_sizes
+
+    def form_device(self, d_form, nimages, stream=0):
+        """compress="lz77" only: four int32 per image of the last encode() call into the device array d_form, on `stream` -- the form
+        taken (0 stored, 1 Huffman-only, 2 matches), the parse's tokens, its matches, the match-form stream's bytes"""
+        if not self.lz77:
+            raise MdcError(ERR_ARG, "PngEncoder.form_device: a Huffman-only encoder has one form")
+        self._check(self._L.mdcl_form_device(self._h, d_form, int(nimages), _stream(stream)))
+
+    def profile(self, on=True):
+        """compress="lz77" only: HIP events around the stages of every encode() call from now on (kernel_ms reads the last call's)"""
+        self._check(self._L.mdcl_profile(self._h, int(bool(on))))
+
+    def kernel_ms(self):
+        """-> (filter, order, match, parse, tally, build, scan, pack, finish + checksum) of the last timed call, in ms; waits for it"""
+        ms = (_f * 9)()
+        self._check(self._L.mdcl_kernel_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
 
 
 PNGD_PATHS = {1: "parallel", 2: "stored", 3: "general"}  # MDCI_PATH_*

@@ -1,4 +1,5 @@
-// rectifyDataset <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1]: a sequence, rectified, as a dataset
+// rectifyDataset <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1] [compress=huffman|lz77] [chain=N]: a sequence,
+// rectified, as a dataset
 // of its own.  The key=value arguments may stand in any position behind the two folders; a bare number is the JPEG quality.
 // The frames are those of playDataset's saving mode -- getImage(i, true, false, false, false), encoded by include/mdc_jenc.h with the
 // bytes cv::imwrite gives a CV_32F image -- but they go into one images.zip of stored %05d.jpg entries, built on the device by
@@ -10,6 +11,10 @@
 //   pcalib.txt   copied verbatim (if present)
 // frames=png: images.zip holds %05d.png entries instead, 8-bit, lossless: the same rectified float frames converted as the JPEG
 // encoder converts them (rintf, clamped to 0..255, NaN -> 0) and encoded on the device by include/mdc_pngw.h; no JPEG encoder is made.
+// compress=lz77 (with frames=png only; chain=N, 1..64, default 4, is its match depth) encodes the frames, and vignette.png, by
+// include/mdc_pnglz.h instead: the same pixels in files that are never larger.  Such files carry distance codes, which the reader
+// decodes on the host unless MDC_GPU_PNG=2 sends them to the device decoder's general path.  The default, compress=huffman, writes
+// today's files byte for byte.  A bad value is refused with one line before anything is opened or created.
 // vignette.png is NOT exported by default, and the exported dataset then opens with validVignette == false, as any dataset without
 // that file does.  vignette=1 writes <out>/vignette.png, 16-bit, if the source has a valid vignette (one line says so if not):
 //   V = the source's vignetteMap (normalised to a maximum of 1; not the inverse);  R = undistort<float>(V) through the sequence's
@@ -37,6 +42,7 @@
 #include "mdc_hip.h"
 #include "mdc_host.h"
 #include "mdc_jenc.h"
+#include "mdc_pnglz.h"
 #include "mdc_pngw.h"
 #include "mdc_zipw.h"
 
@@ -73,7 +79,8 @@ static std::vector<std::string> time_lines(const std::string& file, bool* presen
 }
 
 // The rectified vignette as <out>/vignette.png (the rule is in the header comment).  Returns 0, also when the source has none.
-static int export_vignette(DatasetReader* reader, const std::string& dataset, const std::string& out, int w, int h) {
+// chain > 0: through include/mdc_pnglz.h with that match depth.
+static int export_vignette(DatasetReader* reader, const std::string& dataset, const std::string& out, int w, int h, int chain) {
   mdc_ctx* ctx = reader->getContext();
   const Eigen::Vector2i in = reader->getUndistorter()->getInputDims();
   const size_t n_in = (size_t)in[0] * in[1], n_out = (size_t)w * h;
@@ -101,6 +108,7 @@ static int export_vignette(DatasetReader* reader, const std::string& dataset, co
     }
   }
   mdcp_encoder* enc = 0;
+  mdcl_encoder* lenc = 0;
   uint16_t* d_q = 0;
   uint8_t* d_png = 0;
   int32_t* d_size = 0;
@@ -108,12 +116,17 @@ static int export_vignette(DatasetReader* reader, const std::string& dataset, co
   int32_t size = 0;
   int status = 1;
   std::vector<uint8_t> file;
-  if (mdcp_create(reader->getDevice(), w, h, 16, MDCP_FILTER_ADAPTIVE, 1, &enc) != MDCP_OK || mdcp_output_device(enc, &d_png, &slot, &d_size) != MDCP_OK) {
+  if (chain > 0 && (mdcl_create(reader->getDevice(), w, h, MDCL_GRAY16, MDCL_FILTER_ADAPTIVE, chain, 1, &lenc) != MDCL_OK ||
+                    mdcl_output_device(lenc, &d_png, &slot, &d_size) != MDCL_OK)) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdcl_last_error());
+  } else if (chain <= 0 && (mdcp_create(reader->getDevice(), w, h, 16, MDCP_FILTER_ADAPTIVE, 1, &enc) != MDCP_OK ||
+                            mdcp_output_device(enc, &d_png, &slot, &d_size) != MDCP_OK)) {
     fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
   } else if (mdc_device_alloc(ctx, n_out * sizeof(uint16_t), (void**)&d_q) != MDC_OK || mdc_copy_to_device(ctx, d_q, q.data(), n_out * sizeof(uint16_t)) != MDC_OK) {
     fprintf(stderr, "rectifyDataset: %s\n", mdc_last_error(ctx));
-  } else if (mdcp_encode_u16_device(enc, d_q, (int64_t)n_out, 1, d_png, slot, d_size, 0) != MDCP_OK) {
-    fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
+  } else if (chain > 0 ? mdcl_encode_u16_device(lenc, d_q, (int64_t)n_out, 1, d_png, slot, d_size, 0) != MDCL_OK
+                       : mdcp_encode_u16_device(enc, d_q, (int64_t)n_out, 1, d_png, slot, d_size, 0) != MDCP_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", chain > 0 ? mdcl_last_error() : mdcp_last_error());
   } else if (mdc_copy_to_host(ctx, &size, d_size, sizeof size) != MDC_OK || size <= 0 || size > slot ||
              (file.resize((size_t)size), mdc_copy_to_host(ctx, file.data(), d_png, (size_t)size)) != MDC_OK) {
     fprintf(stderr, "rectifyDataset: reading vignette.png back failed: %s\n", mdc_last_error(ctx));
@@ -125,23 +138,38 @@ static int export_vignette(DatasetReader* reader, const std::string& dataset, co
   }
   if (d_q) mdc_device_free(ctx, d_q);
   mdcp_destroy(enc);
+  mdcl_destroy(lenc);
   if (!status) printf("vignette.png: %d x %d, 16-bit, %d bytes, %zu border pixels at 65535\n", w, h, (int)size, border);
   return status;
 }
 
 int main(int argc, char** argv) {
-  const char* usage = "usage: %s <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1]\n";
+  const char* usage = "usage: %s <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1] [compress=huffman|lz77] [chain=N]\n";
   if (argc < 3) {
     fprintf(stderr, usage, argv[0]);
     return 1;
   }
   std::string dataset = argv[1], out = argv[2];
   int quality = 95;
-  bool png = false, vignette = false;
+  bool png = false, vignette = false, lz77 = false, chain_given = false;
+  int chain = 4;
   for (int i = 3; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "frames=png" || a == "frames=jpg") png = a == "frames=png";
     else if (a == "vignette=1" || a == "vignette=0") vignette = a == "vignette=1";
+    else if (a == "compress=huffman" || a == "compress=lz77") lz77 = a == "compress=lz77";
+    else if (a.compare(0, 6, "chain=") == 0) {
+      char* end = 0;
+      const long v = strtol(a.c_str() + 6, &end, 10);
+      if (end == a.c_str() + 6 || *end || v < 1 || v > MDCL_MAX_CHAIN) {
+        fprintf(stderr, "rectifyDataset: %s: chain is a number 1..%d\n", argv[i], MDCL_MAX_CHAIN);
+        return 1;
+      }
+      chain = (int)v, chain_given = true;
+    } else if (a.compare(0, 9, "compress=") == 0) {
+      fprintf(stderr, "rectifyDataset: %s: compress is huffman or lz77\n", argv[i]);
+      return 1;
+    }
     else if (a.compare(0, 8, "quality=") == 0) quality = atoi(a.c_str() + 8);
     else if (a.find('=') == std::string::npos) quality = atoi(argv[i]);
     else {
@@ -149,6 +177,14 @@ int main(int argc, char** argv) {
       fprintf(stderr, usage, argv[0]);
       return 1;
     }
+  }
+  if (lz77 && !png) {
+    fprintf(stderr, "rectifyDataset: compress=lz77 needs frames=png\n");
+    return 1;
+  }
+  if (chain_given && !lz77) {
+    fprintf(stderr, "rectifyDataset: chain=%d needs compress=lz77\n", chain);
+    return 1;
   }
   if (dataset.empty() || dataset[dataset.size() - 1] != '/') dataset += "/";  // the reader wants the trailing slash
   while (out.size() > 1 && out[out.size() - 1] == '/') out.erase(out.size() - 1);
@@ -166,14 +202,20 @@ int main(int argc, char** argv) {
     delete reader;
     return 1;
   }
-  if (png) printf("Rectifying %s: %d frames of %d x %d into %s (PNG, 8-bit, lossless)\n", dataset.c_str(), total, w, h, out.c_str());
+  if (lz77) printf("Rectifying %s: %d frames of %d x %d into %s (PNG, 8-bit, lossless, LZ77 matches of depth %d)\n", dataset.c_str(), total, w, h, out.c_str(), chain);
+  else if (png) printf("Rectifying %s: %d frames of %d x %d into %s (PNG, 8-bit, lossless)\n", dataset.c_str(), total, w, h, out.c_str());
   else printf("Rectifying %s: %d frames of %d x %d into %s (JPEG quality %d)\n", dataset.c_str(), total, w, h, out.c_str(), quality);
 
   const int chunk = total < 128 ? (total > 0 ? total : 1) : 128;
   const size_t frame = (size_t)w * h;
   mdcj_encoder* enc = 0;
   mdcp_encoder* penc = 0;
-  if (png && mdcp_create(reader->getDevice(), w, h, 8, MDCP_FILTER_ADAPTIVE, chunk, &penc) != MDCP_OK) {
+  mdcl_encoder* lenc = 0;
+  if (lz77 && mdcl_create(reader->getDevice(), w, h, MDCL_GRAY8, MDCL_FILTER_ADAPTIVE, chain, chunk, &lenc) != MDCL_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdcl_last_error());
+    return 1;
+  }
+  if (png && !lz77 && mdcp_create(reader->getDevice(), w, h, 8, MDCP_FILTER_ADAPTIVE, chunk, &penc) != MDCP_OK) {
     fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
     return 1;
   }
@@ -189,8 +231,9 @@ int main(int argc, char** argv) {
     fprintf(stderr, "rectifyDataset: %s\n", mdc_last_error(ctx));
     return 1;
   }
-  if (png ? mdcp_output_device(penc, &d_out, &slot, &d_sizes) != MDCP_OK : mdcj_output_device(enc, &d_out, &slot, &d_sizes) != MDCJ_OK) {
-    fprintf(stderr, "rectifyDataset: %s\n", png ? mdcp_last_error() : mdcj_last_error());
+  if (lz77 ? mdcl_output_device(lenc, &d_out, &slot, &d_sizes) != MDCL_OK
+           : png ? mdcp_output_device(penc, &d_out, &slot, &d_sizes) != MDCP_OK : mdcj_output_device(enc, &d_out, &slot, &d_sizes) != MDCJ_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", lz77 ? mdcl_last_error() : png ? mdcp_last_error() : mdcj_last_error());
     return 1;
   }
   mdcz_writer* zip = 0;
@@ -213,9 +256,10 @@ int main(int argc, char** argv) {
       break;
     }
     // positions without a frame are encoded too (whatever they hold is a legal input) and left out of the archive
-    if (png ? mdcp_encode_f32_device(penc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCP_OK
-            : mdcj_encode_f32_device(enc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJ_OK) {
-      fprintf(stderr, "rectifyDataset: %s\n", png ? mdcp_last_error() : mdcj_last_error());
+    if (lz77 ? mdcl_encode_f32_device(lenc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCL_OK
+        : png ? mdcp_encode_f32_device(penc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCP_OK
+              : mdcj_encode_f32_device(enc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJ_OK) {
+      fprintf(stderr, "rectifyDataset: %s\n", lz77 ? mdcl_last_error() : png ? mdcp_last_error() : mdcj_last_error());
       status = 1;
       break;
     }
@@ -232,6 +276,7 @@ int main(int argc, char** argv) {
   mdc_device_free(ctx, d_frames);
   mdcj_destroy(enc);
   mdcp_destroy(penc);
+  mdcl_destroy(lenc);
   if (status) {
     mdcz_abort(zip);
     delete reader;
@@ -276,7 +321,7 @@ int main(int argc, char** argv) {
     }
   }
   if (!vignette) printf("vignette.png is not exported (a rectified vignette is out of scope): the dataset opens without a vignette.\n");
-  else if (export_vignette(reader, dataset, out, w, h) != 0) status = 1;
+  else if (export_vignette(reader, dataset, out, w, h, lz77 ? chain : 0) != 0) status = 1;
   delete reader;
   return status;
 }

@@ -1,0 +1,263 @@
+"""include/mdc_pnglz.h without a GPU: every directed problem of tests/pnglz_problems.py keeps the property it exists for; zlib
+inflates every restated IDAT to the filtered bytes and PIL reads every file back to the pixels; the token invariants; the files
+that take no match are the Huffman-only restatement's, and none is larger; the smooth frame's ratio; header, library and ctypes
+table are one set; the argument errors come without a device; the kernels' scratch, register and LDS budgets; and the code builder
+as a stand-alone host program under the sanitizers, against the restatement on directed histograms."""
+import ctypes
+import io
+import os
+import subprocess
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+import pnglz_problems as Q
+import pnglz_restatement as Z
+import pngw_restatement as P
+from test_abi import declared, exported, prototypes, signature_mismatches
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PROBLEMS = Q.problems()
+
+
+@pytest.mark.parametrize("name", [p[0] for p in PROBLEMS])
+def test_problem_keeps_its_property_and_its_files_are_read(name):
+    from PIL import Image
+
+    _, img, kind, filt, prop = next(p for p in PROBLEMS if p[0] == name)
+    R = Q.restated(name)
+    assert prop(R), name
+    F = len(R["data"])
+    assert F == img.shape[0] * (1 + img.shape[1] * (1, 2, 3)[kind])
+    for chain in Q.CHAINS:
+        toks = R["tokens"][chain]
+        at = 0
+        for p, length, dist in toks:  # the invariants
+            assert p == at and (dist == 0 and length == 1 or 4 <= length <= 258 and 1 <= dist <= 32768 and dist <= p)
+            assert p // 4096 == (p + length - 1) // 4096
+            if dist:
+                assert R["data"][p:p + length] == bytes(R["data"][p - dist + j % dist] for j in range(length))
+            at += length
+        assert at == F
+        png, (form, ntok, nmatch, L) = R["file"][chain], R["info"][chain]
+        assert ntok == len(toks) and nmatch == len(Q.matches(toks))
+        assert zlib.decompress(P.idat_of(png)) == R["data"]
+        back = np.array(Image.open(io.BytesIO(png)))
+        assert back.shape == img.shape and np.array_equal(back.astype(np.uint16), img.astype(np.uint16))
+        assert len(png) <= len(R["huffman_only"])
+        assert ((png[43] >> 1) & 3) == (0 if form == Z.STORED else 2)
+        if form != Z.MATCHES:
+            assert png == R["huffman_only"]
+        else:
+            assert len(png) == 63 + L < len(R["huffman_only"])
+        if nmatch == 0:
+            assert form != Z.MATCHES
+
+
+def test_the_problems_cover_every_form_and_kind():
+    forms = {Q.restated(p[0])["form"][c] for p in PROBLEMS for c in Q.CHAINS}
+    assert forms == {Z.STORED, Z.HUFFMAN, Z.MATCHES} and {p[2] for p in PROBLEMS} == {Z.GRAY8, Z.GRAY16, Z.RGB8}
+    assert {p[3] for p in PROBLEMS if p[2] != Z.GRAY8} == {0, 1, 2, 3, 4, P.ADAPTIVE}
+
+
+def test_symbol_maps_are_rfc_1951s():
+    for length in range(4, 259):
+        s, e, nb = Z.length_symbol(length)
+        base, bits = Z.LENGTH_BASE[s - 257]
+        assert bits == nb and base + e == length and 0 <= e < (1 << nb) and (length == 258) == (s == 285)
+    for dist in range(1, 32769):
+        s, e, nb = Z.distance_symbol(dist)
+        base, bits = Z.DIST_BASE[s]
+        assert bits == nb and base + e == dist and 0 <= e < (1 << nb)
+
+
+def test_smooth_frame_is_at_most_085_of_the_huffman_only_file():
+    from mono_dataset_code_amd import synth
+
+    img = synth.smooth_frame(640, 480, 0).reshape(480, 640)
+    png, (form, _, _, _) = Z.encode(img, Z.GRAY8, P.ADAPTIVE, 4)
+    plain = P.encode(img, 8, P.ADAPTIVE)[0]
+    print("smooth frame: %d bytes with matches, %d Huffman-only, ratio %.4f" % (len(png), len(plain), len(png) / len(plain)))
+    assert form == Z.MATCHES and len(png) <= 0.85 * len(plain)
+    assert zlib.decompress(P.idat_of(png)) == P.filtered(img, 8, P.ADAPTIVE).tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ header, library, table
+
+
+def test_header_parses_as_c99_and_cxx(tmp_path):
+    src = tmp_path / "pnglz_abi.c"
+    src.write_text('#include "mdc_pnglz.h"\nint main(void){ mdcl_encoder* e = 0; (void)e;'
+                   ' return MDCL_OK + (mdcl_png_bound(1, 1, MDCL_GRAY8) < 0) + MDCL_FILTER_ADAPTIVE + MDCL_MAX_CHAIN + MDCL_FORM_MATCHES + MDCL_KERNELS; }\n')
+    inc = os.path.join(ROOT, "include")
+    for cmd in (["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I" + inc, str(src)],
+                ["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-I" + inc, str(src)]):
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+
+
+def test_header_library_and_table_are_one_set():
+    from mono_dataset_code_amd import build, capi
+
+    names = declared("mdc_pnglz.h", "mdcl_")
+    assert len(names) == 12 and {"mdcl_encode_rgb8_device", "mdcl_form_device", "mdcl_png_bound"} <= set(names)
+    assert exported(build.LIB_PNGLZ) == names == sorted(capi.PNGLZ_API)
+    protos = prototypes("mdc_pnglz.h", "mdcl_")
+    assert sorted(protos) == names
+    assert signature_mismatches(capi.PNGLZ_API, protos) == []
+    wrong = dict(capi.PNGLZ_API, mdcl_png_bound=(ctypes.c_int64, [ctypes.c_int, ctypes.c_int64, ctypes.c_int]))
+    assert len(signature_mismatches(wrong, protos)) == 1
+    L = capi.pnglz_lib()
+    assert sorted(vars(L)) == names
+    hdr = open(os.path.join(ROOT, "include", "mdc_pnglz.h")).read()
+    for text in ("#define MDCL_FILTER_ADAPTIVE %d\n" % P.ADAPTIVE, "#define MDCL_MAX_CHAIN %d\n" % Z.MAX_CHAIN, "#define MDCL_GRAY16 %d\n" % Z.GRAY16,
+                 "#define MDCL_RGB8 %d\n" % Z.RGB8, "#define MDCL_FORM_MATCHES %d\n" % Z.MATCHES, "#define MDCL_FORM_HUFFMAN %d\n" % Z.HUFFMAN):
+        assert text in hdr, text
+    # the two Huffman-only libraries are what they were: none of these names
+    for lib in (build.LIB_PNGW, build.LIB_PNGW_RGB):
+        assert not [n for n in exported(lib) if n.startswith("mdcl_")]
+
+
+def test_library_links_the_zip_writer_only_and_only_the_program_links_it():
+    from mono_dataset_code_amd import build
+
+    for lib in (build.LIB_HIP, build.LIB_HOST, build.LIB_MULTI, build.LIB_BENCH, build.LIB_JENC, build.LIB_ZIPW, build.LIB_PNGW, build.LIB_PNGW_RGB, build.LIB_PNGD):
+        assert "mdcl_" not in subprocess.run(["nm", "-D", lib], stdout=subprocess.PIPE, text=True, check=True).stdout, lib
+        assert "libmdc_pnglz" not in subprocess.run(["readelf", "-d", lib], stdout=subprocess.PIPE, text=True, check=True).stdout, lib
+    needed = subprocess.run(["readelf", "-d", build.LIB_PNGLZ], stdout=subprocess.PIPE, text=True, check=True).stdout
+    ours = sorted({w.strip("[]") for line in needed.splitlines() if "NEEDED" in line for w in line.split() if "libmdc_" in w})
+    assert ours == ["libmdc_zipw.so"], ours
+    assert "$ORIGIN" in needed
+    undefined = subprocess.run(["nm", "-D", "--undefined-only", build.LIB_PNGLZ], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert sorted(w for w in undefined.split() if w.startswith("mdc")) == ["mdcz_crc32_device", "mdcz_last_error"]
+    assert "libmdc_pnglz.so" in subprocess.run(["readelf", "-d", build.RECTIFY_DATASET], stdout=subprocess.PIPE, text=True, check=True).stdout
+    for f in (build.PNGLZ_SOURCE, build.PNGLZ_BLOCK, build.PNGLZ_EXPORT_MAP, os.path.join(ROOT, "include", "mdc_pnglz.h")):
+        assert os.path.exists(f) and f not in set(build.HIP_DEPS) | set(build.HOST_DEPS), f
+
+
+def test_program_names_the_new_arguments_and_refuses_bad_values(tmp_path):
+    from mono_dataset_code_amd import build
+
+    r = subprocess.run([build.RECTIFY_DATASET, str(tmp_path / "seq")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=60, cwd=str(tmp_path))
+    assert r.returncode != 0 and "[compress=huffman|lz77]" in r.stderr and "[chain=N]" in r.stderr and "[frames=jpg|png]" in r.stderr and "[vignette=0|1]" in r.stderr
+    for bad in (["compress=gzip"], ["compress=lz77", "frames=png", "chain=0"], ["compress=lz77", "frames=png", "chain=65"], ["compress=lz77", "frames=png", "chain=4x"],
+                ["compress=lz77", "frames=jpg"], ["compress=lz77"], ["frames=png", "chain=4"]):
+        r = subprocess.run([build.RECTIFY_DATASET, str(tmp_path / "seq"), str(tmp_path / "out")] + bad, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=60, cwd=str(tmp_path))
+        assert r.returncode != 0 and r.stdout == "" and len(r.stderr.splitlines()) == 1, (bad, r.stderr)
+    assert os.listdir(str(tmp_path)) == []
+
+
+def _err(L):
+    return L.mdcl_last_error().decode()
+
+
+def test_bound_and_argument_errors_without_a_device():
+    """every check below comes before any HIP call: a status and a message, never a fault"""
+    from mono_dataset_code_amd import capi
+
+    L, G, C3 = capi.pnglz_lib(), capi.pngw_lib(), capi.pngw_rgb_lib()
+    for w, h in ((1, 1), (5, 3), (17, 5), (640, 480), (65535, 2), (21845, 3)):
+        assert L.mdcl_png_bound(w, h, Z.GRAY8) == G.mdcp_png_bound(w, h, 8) and L.mdcl_png_bound(w, h, Z.GRAY16) == G.mdcp_png_bound(w, h, 16)
+        assert L.mdcl_png_bound(w, h, Z.RGB8) == C3.mdcp_png_bound_rgb8(w, h)
+    assert L.mdcl_png_bound(0, 1, 0) == -1 and L.mdcl_png_bound(1, 1, 3) == -1 and L.mdcl_png_bound(1, 1, -1) == -1 and L.mdcl_png_bound(46339, 46339, 0) == -1
+    h = ctypes.c_void_p()
+    assert L.mdcl_create(0, 4, 4, 0, 0, 4, 1, None) == -1 and "null" in _err(L)
+    assert L.mdcl_create(0, 4, 4, 3, 0, 4, 1, ctypes.byref(h)) == -1 and "kind" in _err(L) and not h.value
+    assert L.mdcl_create(0, 4, 4, 0, 6, 4, 1, ctypes.byref(h)) == -1 and "filter" in _err(L)
+    assert L.mdcl_create(0, 4, 4, 0, -1, 4, 1, ctypes.byref(h)) == -1 and "filter" in _err(L)
+    assert L.mdcl_create(0, 4, 4, 0, 0, 0, 1, ctypes.byref(h)) == -1 and "chain" in _err(L)
+    assert L.mdcl_create(0, 4, 4, 0, 0, 65, 1, ctypes.byref(h)) == -1 and "chain" in _err(L)
+    assert L.mdcl_create(0, 4, 4, 0, 0, 4, 0, ctypes.byref(h)) == -1 and "max_images" in _err(L)
+    assert L.mdcl_create(0, 0, 4, 0, 0, 4, 1, ctypes.byref(h)) == -3 and "start at 1" in _err(L)
+    assert L.mdcl_create(0, 46341, 46341, 0, 0, 4, 1, ctypes.byref(h)) == -3 and "2^31" in _err(L)
+    # the scratch formula of the header: 152 bytes per 16 filtered bytes and 4232 per image
+    F = 20000 * 40001
+    per_image = 152 * ((F + 15) // 16) + 4232
+    fits = (1 << 40) // per_image
+    assert L.mdcl_create(0, 20000, 20000, 1, 0, 4, fits + 1, ctypes.byref(h)) == -3 and "2^40" in _err(L) and str(per_image) in _err(L) and not h.value
+    p = ctypes.c_void_p(4096)  # never dereferenced on the host
+    for fn in (L.mdcl_encode_u8_device, L.mdcl_encode_u16_device, L.mdcl_encode_f32_device, L.mdcl_encode_rgb8_device):
+        assert fn(None, p, 16, 1, p, 1 << 20, p, None) == -1 and "null" in _err(L)
+    assert L.mdcl_output_device(None, None, None, None) == -1 and L.mdcl_form_device(None, p, 1, None) == -1
+    assert L.mdcl_profile(None, 1) == -1 and L.mdcl_kernel_ms(None, None) == -1
+    L.mdcl_destroy(None)
+    with pytest.raises(capi.MdcError):
+        capi.PngEncoder(4, 4, compress="gzip")
+
+
+def test_kernels_have_no_scratch_no_float_atomics_and_keep_their_budgets():
+    """the figures reached: 256 VGPRs for the code builder (one workgroup of 256 per image, two lanes do the serial part), 72 for every
+    other kernel; 24 KiB of LDS for the two blocks
+    the code builder holds side by side, 17 KiB for the ordering's counts, 4 KiB and less elsewhere"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_stats
+
+    ks = isa_stats.kernels(isa_stats.device_asm("mdc_pnglz.hip"))
+    names = sorted(k["pretty"] for k in ks)
+    assert names == sorted(["pnglz_build_kernel", "pnglz_crc_kernel", "pnglz_filter_kernel<Rgb8, 3>", "pnglz_filter_kernel<float, 1>",
+                            "pnglz_filter_kernel<unsigned char, 1>", "pnglz_filter_kernel<unsigned short, 2>", "pnglz_finish_kernel", "pnglz_match_kernel",
+                            "pnglz_order_kernel", "pnglz_pack_kernel", "pnglz_parse_kernel", "pnglz_scan_kernel", "pnglz_tally_kernel"]), names
+    lds = {"pnglz_build_kernel": 24576, "pnglz_order_kernel": 17408}
+    for k in ks:
+        assert k["scratch"] == 0, (k["pretty"], k["scratch"])
+        assert not any(n.startswith("v_mfma") for n in k["counts"]), k["pretty"]
+        assert k["vgpr"] <= (256 if k["pretty"] == "pnglz_build_kernel" else 72), (k["pretty"], k["vgpr"])
+        assert k["lds"] <= lds.get(k["pretty"], 4096), (k["pretty"], k["lds"])
+        assert not any("atomic" in n and ("f32" in n or "f64" in n or "cmpswap" in n) for n in k["counts"]), (k["pretty"], k["counts"])
+    by = {k["pretty"]: k["counts"] for k in ks}
+    assert by["pnglz_scan_kernel"].get("global_load_dwordx4", 0) >= 2 and by["pnglz_pack_kernel"].get("global_load_dwordx4", 0) >= 2
+    assert by["pnglz_match_kernel"].get("global_load_dwordx2", 0) >= 2  # 8 bytes per comparison step
+    assert by["pnglz_pack_kernel"].get("global_atomic_or", 0) >= 1 and by["pnglz_tally_kernel"].get("global_atomic_add", 0) >= 1
+
+
+# ------------------------------------------------------------------------------------------------ the code builder on the host
+
+
+def block_histograms():
+    """(name, 286 literal/length counts with the end-of-block at 1, 30 distance counts)"""
+    rng = np.random.default_rng(12)
+    fib = P.fibonacci(40)
+    out = []
+
+    def case(name, ll, d):
+        ll = list(ll) + [0] * (286 - len(ll))
+        ll[256] = 1
+        out.append((name, ll, list(d) + [0] * (30 - len(d))))
+
+    case("end_of_block_only", [], [])
+    case("one_literal", [0] * 65 + [9], [])
+    case("no_distance", rng.integers(0, 50, 256).tolist(), [])
+    case("one_distance_symbol", [3] + [0] * 256 + [0, 7], [7])
+    case("last_distance_symbol_only", [5] * 256 + [0] + [1] * 29, [0] * 29 + [4])
+    case("every_symbol_equal", [5] * 286, [5] * 30)
+    case("fibonacci_literals_and_distances", fib + [0] * 216 + [0] + fib[:29], fib[:30])
+    case("fibonacci_shuffled", rng.permutation(fib + [0] * 216).tolist() + [0] + [2] * 20, rng.permutation(fib[:30]).tolist())
+    case("length_258_only", [1000, 1], [0, 0, 0, 0, 0, 0, 3])
+    out[-1][1][285] = 3
+    case("large_counts", rng.integers(0, 2 ** 31, 286, dtype=np.int64).tolist(), rng.integers(0, 2 ** 31, 30, dtype=np.int64).tolist())
+    case("long_zero_runs", [1] + [0] * 140 + [2] + [0] * 114 + [0] + [0] * 10 + [3], [0] * 12 + [1] + [0] * 10 + [2])
+    return out
+
+
+def test_code_builder_as_a_host_program_under_the_sanitizers(tmp_path):
+    from mono_dataset_code_amd import build
+
+    exe = build.build_pnglz_block_program(str(tmp_path / "pnglz_block"))
+    cases = block_histograms()
+    text = "".join(" ".join(str(v) for v in ll + d) + "\n" for _, ll, d in cases)
+    r = subprocess.run([exe], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(cases)
+    for (name, ll, d), line in zip(cases, lines):
+        lens, sizes, words = (part.split() for part in line.split("|"))
+        ll_len, d_len, bits = Z.block_codes(ll, d)
+        assert [int(v) for v in lens] == ll_len + d_len, name
+        data = sum(ll[s] * (ll_len[s] + (Z.LENGTH_BASE[s - 257][1] if s > 256 else 0)) for s in range(286) if s != 256)
+        data += sum(d[s] * (d_len[s] + Z.DIST_BASE[s][1]) for s in range(30))
+        assert [int(v) for v in sizes] == [bits.n, (bits.n + data + ll_len[256] + 7) // 8, data], name
+        assert int.from_bytes(b"".join(int(w, 16).to_bytes(4, "little") for w in words), "little") == bits.value, name
+        assert max(ll_len + d_len) <= 15
