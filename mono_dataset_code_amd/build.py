@@ -278,13 +278,15 @@ def build_zipw(force=False):
 LIB_PNGW = os.path.join(PKG, "libmdc_pngw.so")
 PNGW_SOURCE = os.path.join(CSRC, "mdc_pngw.hip")
 PNGW_EXPORT_MAP = os.path.join(CSRC, "mdc_pngw_exports.map")
+PNG_BLOCK = os.path.join(CSRC, "png_block.h")  # the DEFLATE block builder, plain C++: the three PNG encoder libraries and a CPU test program
+PNG_ENCODE_CORE = os.path.join(CSRC, "png_encode_core.h")  # what else the three share: filter helpers, stream placement, framing, host helpers
 
 
 def build_pngw(force=False):
-    """libmdc_pngw.so: the device PNG encoder (include/mdc_pngw.h) -- one translation unit on top of libmdc_zipw.so (for the IDAT
-    chunk's CRC-32), independent of libmdc_hip.so and outside its build identity."""
+    """libmdc_pngw.so: the device PNG encoder (include/mdc_pngw.h) -- one translation unit and the two headers it shares with
+    mdc_pnglz.hip, on top of libmdc_zipw.so (for the IDAT chunk's CRC-32), independent of libmdc_hip.so and outside its build identity."""
     build_zipw(force)
-    if force or _stale(LIB_PNGW, [PNGW_SOURCE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_zipw.h"), PNGW_EXPORT_MAP, LIB_ZIPW]):
+    if force or _stale(LIB_PNGW, [PNGW_SOURCE, PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_zipw.h"), PNGW_EXPORT_MAP, LIB_ZIPW]):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGW_EXPORT_MAP, "-o", LIB_PNGW])
     return LIB_PNGW
@@ -298,7 +300,7 @@ def build_pngw_rgb(force=False):
     """libmdc_pngw_rgb.so: the device PNG encoder for 8-bit RGB images (include/mdc_pngw_rgb.h) -- mdc_pngw.hip built with
     -DMDCP_RGB8_LIBRARY, a library of its own beside libmdc_pngw.so (which stays what it is), on top of libmdc_zipw.so."""
     build_zipw(force)
-    if force or _stale(LIB_PNGW_RGB, [PNGW_SOURCE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pngw_rgb.h"), os.path.join(INC, "mdc_zipw.h"),
+    if force or _stale(LIB_PNGW_RGB, [PNGW_SOURCE, PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pngw_rgb.h"), os.path.join(INC, "mdc_zipw.h"),
                                       PNGW_RGB_EXPORT_MAP, LIB_ZIPW]):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-DMDCP_RGB8_LIBRARY=1", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN",
@@ -308,24 +310,24 @@ def build_pngw_rgb(force=False):
 
 LIB_PNGLZ = os.path.join(PKG, "libmdc_pnglz.so")
 PNGLZ_SOURCE = os.path.join(CSRC, "mdc_pnglz.hip")
-PNGLZ_BLOCK = os.path.join(CSRC, "pnglz_block.h")
+PNGLZ_BLOCK = PNG_BLOCK  # the name the block builder had while it was libmdc_pnglz.so's alone
 PNGLZ_EXPORT_MAP = os.path.join(CSRC, "mdc_pnglz_exports.map")
 
 
 def build_pnglz(force=False):
     """libmdc_pnglz.so: the device PNG encoder with LZ77 matches (include/mdc_pnglz.h), gray and RGB in one library -- one
-    translation unit plus the code builder it shares with the CPU test program, on top of libmdc_zipw.so; libmdc_pngw.so and
-    libmdc_pngw_rgb.so are not involved, and it is outside libmdc_hip.so's build identity."""
+    translation unit and the two headers it shares with mdc_pngw.hip, on top of libmdc_zipw.so; it links neither libmdc_pngw.so nor
+    libmdc_pngw_rgb.so, and it is outside libmdc_hip.so's build identity."""
     build_zipw(force)
-    if force or _stale(LIB_PNGLZ, [PNGLZ_SOURCE, PNGLZ_BLOCK, os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mdc_zipw.h"), PNGLZ_EXPORT_MAP, LIB_ZIPW]):
+    if force or _stale(LIB_PNGLZ, [PNGLZ_SOURCE, PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mdc_zipw.h"), PNGLZ_EXPORT_MAP, LIB_ZIPW]):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, PNGLZ_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGLZ_EXPORT_MAP, "-o", LIB_PNGLZ])
     return LIB_PNGLZ
 
 
 def build_pnglz_block_program(out, sanitize=True):
-    """tests/native/pnglz_block.cpp: csrc/pnglz_block.h (the code builder and header writer of libmdc_pnglz.so) as a stand-alone
-    program, under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_pnglz_cpu.py).  Pure host code."""
+    """tests/native/pnglz_block.cpp: csrc/png_block.h (the code builder and header writer of the PNG encoder libraries) as a
+    stand-alone program, under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_pnglz_cpu.py).  Pure host code."""
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
     _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pnglz_block.cpp"), "-o", out])
     return out

@@ -1,7 +1,10 @@
 // libmdc_pnglz.so (include/mdc_pnglz.h): PNG files of device-resident images with LZ77 matches in the DEFLATE stream, made on the
-// device.  One translation unit plus pnglz_block.h (the code builder, shared with a host test program); from elsewhere it takes only
-// mdcz_crc32_device (libmdc_zipw.so).  The filter rule, the Adler sums, the code-length rule and the header writer are
-// include/mdc_pngw.h's, restated here: mdc_pngw.hip is not touched, and the equality of the two is a tested fact.
+// device.  One translation unit on top of png_block.h (the DEFLATE block builder, plain C++, also a host test program) and
+// png_encode_core.h (the filter kernel's helpers, stream placement, framing and host helpers), both shared with mdc_pngw.hip: the
+// code-length rule, the header writer, the bit offsets' scan and the framing are one text for the three libraries.  From another
+// library it takes only mdcz_crc32_device (libmdc_zipw.so).  What is this file's own: the layout of the per-image words, the kernels'
+// names, its copy of the filter kernel's body (png_encode_core.h says why), the order, match, parse and tally kernels, the token loops
+// of the scan and pack kernels, and a BitPacker that ORs every word.
 //
 // One call is nine kernels and the checksum, with no host round trip between them:
 //   pnglz_filter_kernel  as pngw_filter_kernel: filtered bytes, their histogram, the Adler-32 partial sums.
@@ -21,23 +24,15 @@
 // All integer, no private memory, every loop bounded by F or a constant.
 #include "../../include/mdc_pnglz.h"
 
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
 #include <new>
 
 #include "../../include/mdc_zipw.h"
-
-#define PNGLZ_HD __host__ __device__ __forceinline__
-#include "pnglz_block.h"
+#include "png_encode_core.h"
 
 namespace {
 
-using namespace pnglz;
+static_assert(MDCL_ERR_ARG == kErrArg && MDCL_ERR_NOMEM == kErrNoMem && MDCL_OK == 0,
+              "png_encode_core.h restates these values of include/mdc_pnglz.h");
 
 constexpr int kHistAt = 0;                    // per image, cleared per call: the filtered bytes' histogram [256]
 constexpr int kAdlerAt = 256;                 //   the Adler sums as two 64-bit words
@@ -47,48 +42,14 @@ constexpr int kZeroWords = kCountAt + 4;      // 580
 constexpr int kHdrAt = kAll;                  // per image: codes [316], header words [144], meta [12]
 constexpr int kMeta = kHdrAt + kHdrWords;     // meta: 0 form, 1 header bits, 2 stream bytes, 3/4 data bits (low, high)
 constexpr int kTabWords = kMeta + 12;         // 472
-constexpr int kStreamAt = 43;                 // signature 8, IHDR 25, length 4, "IDAT" 4, zlib header 2
-constexpr int kRowsPerGroup = 16;
-constexpr int kMaxGrid = 8192;
-constexpr uint32_t kAdlerMod = 65521;
 constexpr uint32_t kCovered = 0xffffffffu;    // in the match array after the parse: inside a match, no token starts here
 constexpr long long kSmallBytes = 4 * (kZeroWords + kTabWords) + 16 + 8;  // + the form record, the checksum's length and result
 
-// ---------------------------------------------------------------------------------------------------- pixels -> filtered bytes
-
-__device__ __forceinline__ int sample_of(uint8_t v) { return v; }
-__device__ __forceinline__ int sample_of(uint16_t v) { return v; }
-struct Rgb8 {  // one pixel of an 8-bit RGB image in file order
-  uint8_t r, g, b;
+struct Layout {
+  static constexpr int zero_words = kZeroWords, adler_at = kAdlerAt, tab_words = kTabWords, meta_at = kMeta;
 };
-__device__ __forceinline__ int sample_of(Rgb8 v) { return ((int)v.r << 16) | ((int)v.g << 8) | (int)v.b; }
-__device__ __forceinline__ int sample_of(float v) {  // as mdcp_encode_f32_device
-  const float r = fminf(fmaxf(rintf(v), 0.0f), 255.0f);
-  return v != v ? 0 : (int)r;
-}
 
-__device__ __forceinline__ int paeth(int a, int b, int c) {
-  const int p = a + b - c;
-  const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
-__device__ __forceinline__ int filter_byte(int type, int x, int a, int b, int c) {
-  const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? ((a + b) >> 1) : paeth(a, b, c);
-  return (x - pred) & 255;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ const T* image_at(const T* images, long long f, long long stride) { return images + f * stride; }
-__device__ __forceinline__ const Rgb8* image_at(const Rgb8* images, long long f, long long stride) {
-  return (const Rgb8*)((const uint8_t*)images + f * stride);
-}
+// ---------------------------------------------------------------------------------------------------- pixels -> filtered bytes
 
 template <typename T, int BPP>
 __global__ __launch_bounds__(256) void pnglz_filter_kernel(const T* __restrict__ images, long long stride, long long nimages, int w, int h, int filter,
@@ -400,21 +361,6 @@ __global__ __launch_bounds__(256) void pnglz_build_kernel(long long nimages, lon
 
 // ---------------------------------------------------------------------------------------------------- bit offsets
 
-struct Slot {  // where an image's DEFLATE stream goes: 32-bit words from the 4-byte boundary at or below byte 43 of the file
-  uint8_t* stream;
-  uint32_t* words;
-  uint32_t shift;
-};
-
-__device__ __forceinline__ Slot slot_of(uint8_t* out, long long slot_bytes, long long f) {
-  Slot s;
-  s.stream = out + f * slot_bytes + kStreamAt;
-  const uint32_t mis = (uint32_t)((uintptr_t)s.stream & 3);
-  s.words = (uint32_t*)(s.stream - mis);
-  s.shift = 8 * mis;
-  return s;
-}
-
 // the bits of the tokens that start in one 16-position unit; lens[s] = the code length of symbol s (distances from 286)
 __device__ __forceinline__ uint32_t unit_bits(const uint4 bytes, const uint4* __restrict__ m4, bool matches, int valid, const uint8_t* __restrict__ lens) {
   const uint32_t d[4] = {bytes.x, bytes.y, bytes.z, bytes.w};
@@ -445,9 +391,7 @@ __global__ __launch_bounds__(1024) void pnglz_scan_kernel(long long nimages, lon
                                                           const uint32_t* __restrict__ match, const uint32_t* __restrict__ tab,
                                                           unsigned long long* __restrict__ offsets, uint8_t* out, long long slot_bytes) {
   __shared__ uint8_t lens[kAll + 4];
-  __shared__ uint32_t wave_total[16];
-  __shared__ unsigned long long carry_s;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const long long nunits = (F + 15) >> 4;
   for (long long f = blockIdx.x; f < nimages; f += gridDim.x) {
     const uint32_t* __restrict__ tb = tab + f * kTabWords;
@@ -455,44 +399,10 @@ __global__ __launch_bounds__(1024) void pnglz_scan_kernel(long long nimages, lon
     if (form == MDCL_FORM_STORED) continue;  // nothing is packed
     __syncthreads();
     if (t < kAll) lens[t] = (uint8_t)(tb[t] >> 16);
-    const Slot sl = slot_of(out, slot_bytes, f);
-    const unsigned long long start = (unsigned long long)sl.shift + tb[kMeta + 1];
-    for (long long wd = t; wd < (long long)((start + 31) >> 5); wd += 1024) sl.words[wd] = 0;
-    if (t == 0) carry_s = start;
-    __syncthreads();
     const uint4* __restrict__ src = (const uint4*)(filt + f * filt_stride);
     const uint4* __restrict__ m4 = (const uint4*)(match + f * filt_stride);
-    unsigned long long* __restrict__ off = offsets + f * nunits;
-    for (long long first = 0; first < nunits; first += 1024) {
-      const long long u = first + t;
-      uint32_t bits = 0;
-      if (u < nunits) {
-        const long long rem = F - u * 16;
-        bits = unit_bits(src[u], m4 + 4 * u, form == MDCL_FORM_MATCHES, rem < 16 ? (int)rem : 16, lens);
-      }
-      uint32_t inc = bits;  // inclusive scan inside the wave: at most 1024 * 768
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t other = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += other;
-      }
-      if (lane == 63) wave_total[wave] = inc;
-      __syncthreads();
-      unsigned long long before = carry_s;
-      for (int k = 0; k < wave; k++) before += wave_total[k];
-      const unsigned long long at = before + inc - bits;
-      if (u < nunits) {
-        off[u] = at;
-        for (unsigned long long wd = (at + 31) >> 5; wd < ((at + bits + 31) >> 5); wd++) sl.words[wd] = 0;
-      }
-      __syncthreads();
-      if (t == 1023) carry_s = before + inc;
-      __syncthreads();
-    }
-    if (t == 0) {  // the end-of-block code
-      const unsigned long long at = carry_s;
-      for (unsigned long long wd = (at + 31) >> 5; wd < ((at + lens[kEob] + 31) >> 5); wd++) sl.words[wd] = 0;
-    }
+    scan_units(slot_of(out, slot_bytes, f), tb[kMeta + 1], F, offsets + f * nunits, lens,
+               [&](long long u, int valid) { return unit_bits(src[u], m4 + 4 * u, form == MDCL_FORM_MATCHES, valid, lens); });
   }
 }
 
@@ -534,21 +444,8 @@ __global__ __launch_bounds__(256) void pnglz_pack_kernel(long long nimages, long
     const uint8_t* __restrict__ src = filt + f * filt_stride;
     const Slot sl = slot_of(out, slot_bytes, f);
     const uint32_t form = tb[kMeta];
-    if (form == MDCL_FORM_STORED) {  // byte idx of the stream is header byte r < 5 or data byte r - 5 of block idx / 65540
-      const long long total = stored_bytes(F);
-      const int last = (int)((F - 1) / 65535);
-      for (long long idx = (long long)p * 256 + t; idx < total; idx += (long long)parts * 256) {
-        const int b = (int)(idx / 65540), r = (int)(idx - (long long)b * 65540);
-        uint8_t v;
-        if (r >= 5) {
-          v = src[(long long)b * 65535 + (r - 5)];
-        } else {
-          const long long left = F - (long long)b * 65535;
-          const uint32_t len = left < 65535 ? (uint32_t)left : 65535u;
-          v = r == 0 ? (uint8_t)(b == last) : r == 1 ? (uint8_t)len : r == 2 ? (uint8_t)(len >> 8) : r == 3 ? (uint8_t)~len : (uint8_t)(~len >> 8);
-        }
-        sl.stream[idx] = v;
-      }
+    if (form == MDCL_FORM_STORED) {
+      pack_stored(sl, src, F, p, parts, t);
       continue;
     }
     const uint32_t* __restrict__ codes = tb;  // 316 words per image, read through the caches
@@ -602,93 +499,25 @@ __global__ __launch_bounds__(256) void pnglz_pack_kernel(long long nimages, long
   }
 }
 
-// head: 33 bytes (signature, IHDR with its CRC) and the 12 of IEND
 __global__ __launch_bounds__(256) void pnglz_finish_kernel(long long nimages, long long F, const uint8_t* __restrict__ head, const uint32_t* __restrict__ zeroed,
                                                            const uint32_t* __restrict__ tab, uint8_t* out, long long slot_bytes, int32_t* __restrict__ sizes,
                                                            int32_t* __restrict__ crc_len) {
-  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nimages; f += (long long)gridDim.x * 256) {
-    uint8_t* __restrict__ o = out + f * slot_bytes;
-    const uint32_t stream = tab[f * kTabWords + kMeta + 2];
-    const uint32_t idat = 2 + stream + 4;
-    for (int i = 0; i < 33; i++) o[i] = head[i];
-    for (int i = 0; i < 4; i++) o[33 + i] = (uint8_t)(idat >> (24 - 8 * i));
-    o[37] = 'I', o[38] = 'D', o[39] = 'A', o[40] = 'T', o[41] = 0x78, o[42] = 0x01;
-    const unsigned long long* __restrict__ sums = (const unsigned long long*)(zeroed + f * kZeroWords + kAdlerAt);
-    const uint32_t s1 = (uint32_t)((1 + sums[0]) % kAdlerMod), s2 = (uint32_t)(((unsigned long long)F + sums[1]) % kAdlerMod);
-    const uint32_t adler = (s2 << 16) | s1;
-    uint8_t* __restrict__ e = o + kStreamAt + stream;
-    for (int i = 0; i < 4; i++) e[i] = (uint8_t)(adler >> (24 - 8 * i));
-    for (int i = 0; i < 12; i++) e[8 + i] = head[33 + i];
-    sizes[f] = (int32_t)(57 + 6 + stream);
-    crc_len[f] = (int32_t)(4 + idat);
-  }
+  finish_files<Layout>(nimages, F, head, zeroed, tab, out, slot_bytes, sizes, crc_len);
 }
 
 __global__ __launch_bounds__(256) void pnglz_crc_kernel(long long nimages, const uint32_t* __restrict__ tab, const uint32_t* __restrict__ crc, uint8_t* out,
                                                         long long slot_bytes) {
-  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nimages; f += (long long)gridDim.x * 256) {
-    uint8_t* __restrict__ e = out + f * slot_bytes + kStreamAt + tab[f * kTabWords + kMeta + 2] + 4;
-    const uint32_t c = crc[f];
-    for (int i = 0; i < 4; i++) e[i] = (uint8_t)(c >> (24 - 8 * i));
-  }
+  crc_bytes<Layout>(nimages, tab, crc, out, slot_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
 
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-uint32_t crc32_host(const uint8_t* p, size_t n) {
-  uint32_t c = 0xFFFFFFFFu;
-  for (size_t i = 0; i < n; i++) {
-    c ^= p[i];
-    for (int b = 0; b < 8; b++) c = (c >> 1) ^ ((c & 1) ? 0xEDB88320u : 0u);
-  }
-  return ~c;
-}
-
-void put_be32(uint8_t* p, uint32_t v) {
-  p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
-}
-
 int bpp_of(int kind) { return kind == MDCL_GRAY8 ? 1 : kind == MDCL_GRAY16 ? 2 : kind == MDCL_RGB8 ? 3 : 0; }
-
-// the stored form's size for rows of 1 + w * bpp bytes; -1 past 2^31 - 1
-int64_t bound_of(int w, int h, int bpp) {
-  if (w < 1 || h < 1 || bpp < 1) return -1;
-  const int64_t row = 1 + (int64_t)w * bpp;  // < 2^33
-  if (row > INT32_MAX / (int64_t)h) return -1;
-  const int64_t bound = 57 + 6 + stored_bytes(row * h);
-  return bound > INT32_MAX ? -1 : bound;
-}
-
-int grid_for(long long items) { return (int)(items < 1 ? 1 : items > kMaxGrid ? kMaxGrid : items); }
 
 }  // namespace
 
 struct mdcl_encoder {
-  int device = -1, w = 0, h = 0, kind = 0, filter = 0, chain = 0, max_images = 0;
+  int device = -1, w = 0, h = 0, kind = 0, bpp = 0, filter = 0, chain = 0, max_images = 0;
   long long F = 0, nunits = 0;
   uint8_t* d_head = nullptr;
   uint8_t* d_filt = nullptr;
@@ -757,10 +586,7 @@ int encode(const char* who, mdcl_encoder* e, const T* d_images, int64_t stride, 
   if (hipMemsetAsync(e->d_zeroed, 0, (size_t)n * kZeroWords * 4, s) != hipSuccess)
     return fail(MDCL_ERR_HIP, "%s: clearing the histograms failed: %s", who, hipGetErrorString(hipGetLastError()));
   const long long groups = ((long long)e->h + kRowsPerGroup - 1) / kRowsPerGroup;
-  long long parts = (e->nunits + 1023) / 1024;
-  if (n * parts < 1024) parts = (1024 + n - 1) / n;  // few images: still fill the device
-  if (parts > (e->nunits + 255) / 256) parts = (e->nunits + 255) / 256;
-  if (parts > 4096) parts = 4096;
+  const long long parts = pack_parts(n, e->nunits);
   const long long chunks = (F + kChunk - 1) / kChunk;
   pnglz_filter_kernel<T, BPP><<<grid_for(n * groups), 256, 0, s>>>(d_images, (long long)stride, n, e->w, e->h, e->filter, e->d_filt, fs, e->d_zeroed);
   mark();
@@ -820,7 +646,7 @@ int mdcl_create(int device, int w, int h, int kind, int filter, int chain, int m
   DeviceGuard dg(device);
   mdcl_encoder* e = new (std::nothrow) mdcl_encoder;
   if (!e) return fail(MDCL_ERR_NOMEM, "%s: out of host memory", who);
-  e->device = device, e->w = w, e->h = h, e->kind = kind, e->filter = filter, e->chain = chain, e->max_images = max_images;
+  e->device = device, e->w = w, e->h = h, e->kind = kind, e->bpp = bpp, e->filter = filter, e->chain = chain, e->max_images = max_images;
   e->F = F, e->nunits = nunits;
   const size_t n = (size_t)max_images;
   if (hipMalloc((void**)&e->d_head, 48) != hipSuccess || hipMalloc((void**)&e->d_filt, n * (size_t)nunits * 16) != hipSuccess ||
@@ -832,14 +658,8 @@ int mdcl_create(int device, int w, int h, int kind, int filter, int chain, int m
     destroy(e);
     return fail(MDCL_ERR_NOMEM, "%s: could not allocate the scratch arrays of %d images of %d x %d", who, max_images, w, h);
   }
-  uint8_t head[48] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n', 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
-  put_be32(head + 16, (uint32_t)w);
-  put_be32(head + 20, (uint32_t)h);
-  head[24] = (uint8_t)(kind == MDCL_GRAY16 ? 16 : 8);
-  head[25] = kind == MDCL_RGB8 ? 2 : 0;  // colour type: truecolour or gray; compression, filter method, interlace: 0
-  put_be32(head + 29, crc32_host(head + 12, 17));
-  const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
-  memcpy(head + 33, iend, 12);
+  uint8_t head[48];
+  png_head(head, w, h, kind == MDCL_GRAY16 ? 16 : 8, kind == MDCL_RGB8 ? 2 : 0);  // colour type: truecolour or gray
   if (hipMemcpy(e->d_head, head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) {
     destroy(e);
     return fail(MDCL_ERR_HIP, "%s: copying the header failed", who);
@@ -871,22 +691,7 @@ int mdcl_encode_rgb8_device(mdcl_encoder* enc, const uint8_t* d_images, int64_t 
 }
 
 int mdcl_output_device(mdcl_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
-  const char* who = "mdcl_output_device";
-  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(MDCL_ERR_ARG, "%s: null argument", who);
-  const int64_t bound = bound_of(enc->w, enc->h, bpp_of(enc->kind));
-  if (!enc->d_out) {
-    DeviceGuard dg(enc->device);
-    uint8_t* o = nullptr;
-    int32_t* z = nullptr;
-    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_images) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_images * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(o);
-      return fail(MDCL_ERR_NOMEM, "%s: could not allocate %d slots of %lld bytes", who, enc->max_images, (long long)bound);
-    }
-    enc->d_out = o, enc->d_sizes = z;
-  }
-  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
-  return MDCL_OK;
+  return output_device("mdcl_output_device", enc, d_out, slot_bytes, d_sizes);
 }
 
 int mdcl_form_device(mdcl_encoder* enc, int32_t* d_form, int nimages, void* stream) {

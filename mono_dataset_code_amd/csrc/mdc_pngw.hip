@@ -1,5 +1,9 @@
-// libmdc_pngw.so (include/mdc_pngw.h): PNG files of device-resident grayscale images, made on the device.  One translation unit;
-// the only thing it takes from elsewhere is mdcz_crc32_device (libmdc_zipw.so) for the IDAT chunk's CRC.
+// libmdc_pngw.so (include/mdc_pngw.h): PNG files of device-resident grayscale images, made on the device.  One translation unit on
+// top of png_block.h (the DEFLATE block builder, plain C++) and png_encode_core.h (the filter kernel's helpers, stream placement,
+// framing and host helpers), both shared with mdc_pnglz.hip; the only thing it takes from another library is mdcz_crc32_device
+// (libmdc_zipw.so) for the IDAT chunk's CRC.  What is this file's own: the layout of the per-image words, the kernels' names, its copy
+// of the filter kernel's body (png_encode_core.h says why), the Huffman-only scan and pack (codes staged in LDS, plain stores for a
+// run's inner words) and the entry points.
 // Built with -DMDCP_RGB8_LIBRARY the same unit is libmdc_pngw_rgb.so (include/mdc_pngw_rgb.h) instead: the 8-bit RGB kind, whose pixel is
 // one 3-byte sample of the filter kernel, with entry points of its own and none of the gray ones -- so the gray library, its kernels
 // and its exported names are what they were, and the two can be loaded side by side.
@@ -25,42 +29,32 @@
 #include "../../include/mdc_pngw_rgb.h"
 #endif
 
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
 #include <new>
 
 #include "../../include/mdc_zipw.h"
-
-#define PNGW_HD __host__ __device__ __forceinline__
+#include "png_encode_core.h"
 
 namespace {
 
-constexpr int kMaxSym = MDCP_MAX_SYMBOLS;
+static_assert(MDCP_MAX_SYMBOLS == kMaxSym && MDCP_ERR_ARG == kErrArg && MDCP_ERR_NOMEM == kErrNoMem && MDCP_OK == 0,
+              "png_block.h and png_encode_core.h restate these values of include/mdc_pngw.h");
+
 constexpr int kLit = 257;            // literals and end-of-block
 constexpr int kSeq = 258;            // code lengths in the header: 257 + one distance code
 constexpr int kHdrWords = 128;       // 17 + 57 + 258 * 14 bits at most: 116 words
 constexpr int kZeroWords = 296;      // per image, cleared per call: histogram [288], Adler sums as two 64-bit words
 constexpr int kTabWords = 400;       // per image: codes [260], header words [128], meta [12]
+constexpr int kHdrAt = 260;
 constexpr int kMeta = 388;           // meta: 0 stored?, 1 header bits, 2 stream bytes, 3/4 data bits (low, high)
-constexpr int kStreamAt = 43;        // signature 8, IHDR 25, length 4, "IDAT" 4, zlib header 2
-constexpr int kRowsPerGroup = 16;
-constexpr int kMaxGrid = 8192;
-constexpr uint32_t kAdlerMod = 65521;
 constexpr long long kSmallBytes = 4 * (kZeroWords + kTabWords) + 8;  // + the checksum's length and result
 
-struct HuffWork {
-  unsigned long long wt[2 * kMaxSym];
-  uint16_t parent[2 * kMaxSym];
-  uint16_t depth[2 * kMaxSym];
-  uint16_t order[kMaxSym];
-  uint32_t count[16], next[16];
+struct Layout {
+  static constexpr int zero_words = kZeroWords, adler_at = kMaxSym, tab_words = kTabWords, meta_at = kMeta;
 };
 
+// The Huffman-only block: png_block.h's rule and bit writer on this unit's own, smaller work area with the two counts of the header
+// fixed at 257 and 1.  png_block.h's build_block gives the same bits (a tested fact), but in pngw_build_kernel it takes 201 VGPRs as it
+// stands and, cut down to this case, 0.02 ms more per 1024 noise frames than this text: so this text stays.
 struct BuildLds {
   uint32_t hist[kMaxSym];
   uint8_t len[kMaxSym];
@@ -74,109 +68,8 @@ struct BuildLds {
   uint32_t meta[12];
 };
 
-// order[r] = the used symbol of rank r by (count, symbol); lanes tid, tid + nthr, ... of the caller take their symbols
-PNGW_HD void huff_order(const uint32_t* hist, int nsym, uint16_t* order, int tid, int nthr) {
-  for (int s = tid; s < nsym; s += nthr) {
-    const uint32_t c = hist[s];
-    if (!c) continue;
-    int r = 0;
-    for (int j = 0; j < nsym; j++) {
-      const uint32_t o = hist[j];
-      r += (o && (o < c || (o == c && j < s))) ? 1 : 0;
-    }
-    order[r] = (uint16_t)s;
-  }
-}
-
-// include/mdc_pngw.h, "Code lengths"; k.order is filled
-PNGW_HD void huff_lengths(const uint32_t* hist, int nsym, int limit, HuffWork& k, uint8_t* len) {
-  int n = 0;
-  for (int s = 0; s < nsym; s++) {
-    len[s] = 0;
-    n += hist[s] ? 1 : 0;
-  }
-  if (n == 0) return;
-  if (n == 1) {
-    len[k.order[0]] = 1;
-    return;
-  }
-  for (int i = 0; i < n; i++) k.wt[i] = hist[k.order[i]];
-  int leaf = 0, inner = n, next = n;
-  while (next < 2 * n - 1) {
-    unsigned long long sum = 0;
-    for (int pick = 0; pick < 2; pick++) {
-      int node;
-      if (leaf < n && (inner >= next || k.wt[leaf] <= k.wt[inner])) node = leaf++;
-      else node = inner++;
-      sum += k.wt[node];
-      k.parent[node] = (uint16_t)next;
-    }
-    k.wt[next++] = sum;
-  }
-  k.depth[2 * n - 2] = 0;
-  for (int node = 2 * n - 3; node >= 0; node--) k.depth[node] = (uint16_t)(k.depth[k.parent[node]] + 1);
-  const uint32_t full = 1u << limit;
-  uint32_t kraft = 0;
-  for (int i = 0; i < n; i++) {
-    const int d = k.depth[i] < limit ? k.depth[i] : limit;
-    len[k.order[i]] = (uint8_t)d;
-    kraft += 1u << (limit - d);
-  }
-  while (kraft > full) {
-    bool any = false;
-    for (int i = 0; i < n && kraft > full; i++) {
-      const int s = k.order[i];
-      if (len[s] < limit) {
-        len[s]++;
-        kraft -= 1u << (limit - len[s]);
-        any = true;
-      }
-    }
-    if (!any) break;  // n > 2^limit: refused before the launch
-  }
-  while (kraft < full) {
-    const uint32_t room = full - kraft;
-    int i = n - 1;
-    while (i >= 0 && !(len[k.order[i]] > 1 && (1u << (limit - len[k.order[i]])) <= room)) i--;
-    if (i < 0) break;  // cannot happen for n >= 2 (the header's argument)
-    const int s = k.order[i];
-    kraft += 1u << (limit - len[s]);
-    len[s]--;
-  }
-}
-
-// codes[s] = the canonical code of symbol s, bit-reversed, | length << 16
-PNGW_HD void canonical(const uint8_t* len, int nsym, int limit, HuffWork& k, uint32_t* codes) {
-  for (int b = 0; b <= limit; b++) k.count[b] = 0;
-  for (int s = 0; s < nsym; s++) k.count[len[s]]++;
-  k.count[0] = 0;
-  uint32_t code = 0;
-  for (int b = 1; b <= limit; b++) {
-    code = (code + k.count[b - 1]) << 1;
-    k.next[b] = code;
-  }
-  for (int s = 0; s < nsym; s++) {
-    const int l = len[s];
-    uint32_t c = l ? k.next[l]++ : 0, r = 0;
-    for (int i = 0; i < l; i++) {
-      r = (r << 1) | (c & 1);
-      c >>= 1;
-    }
-    codes[s] = r | ((uint32_t)l << 16);
-  }
-}
-
-PNGW_HD void put_bits(uint32_t* words, uint32_t& nbits, uint32_t v, int n) {
-  const uint32_t at = nbits & 31;
-  words[nbits >> 5] |= v << at;
-  if (at + n > 32) words[(nbits >> 5) + 1] |= v >> (32 - at);
-  nbits += n;
-}
-
-PNGW_HD long long stored_bytes(long long F) { return F + 5 * ((F + 65534) / 65535); }
-
 // everything of one image's dynamic block that does not depend on the byte positions; L.hist[0..256] and L.work.order are filled
-PNGW_HD void build_block(BuildLds& L, long long F) {
+PNG_HD void build_block(BuildLds& L, long long F) {
   huff_lengths(L.hist, kLit, 15, L.work, L.len);
   canonical(L.len, kLit, 15, L.work, L.codes);
   L.len[kLit] = 0;  // the one distance code
@@ -241,41 +134,6 @@ PNGW_HD void build_block(BuildLds& L, long long F) {
 }
 
 // ---------------------------------------------------------------------------------------------------- pixels -> filtered bytes
-
-__device__ __forceinline__ int sample_of(uint8_t v) { return v; }
-__device__ __forceinline__ int sample_of(uint16_t v) { return v; }
-struct Rgb8 {  // one pixel of an 8-bit RGB image in file order: the filter distance is the pixel, as it is the sample of a gray image
-  uint8_t r, g, b;
-};
-__device__ __forceinline__ int sample_of(Rgb8 v) { return ((int)v.r << 16) | ((int)v.g << 8) | (int)v.b; }
-__device__ __forceinline__ int sample_of(float v) {  // as mdcj_encode_f32_device: cv::Mat::convertTo(CV_8U)
-  const float r = fminf(fmaxf(rintf(v), 0.0f), 255.0f);
-  return v != v ? 0 : (int)r;
-}
-
-__device__ __forceinline__ int paeth(int a, int b, int c) {
-  const int p = a + b - c;
-  const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
-__device__ __forceinline__ int filter_byte(int type, int x, int a, int b, int c) {
-  const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? ((a + b) >> 1) : paeth(a, b, c);
-  return (x - pred) & 255;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// image f of a batch: `stride` elements on, for RGB pixels `stride` bytes on (three-byte pixels, images at any byte distance)
-template <typename T>
-__device__ __forceinline__ const T* image_at(const T* images, long long f, long long stride) { return images + f * stride; }
-__device__ __forceinline__ const Rgb8* image_at(const Rgb8* images, long long f, long long stride) {
-  return (const Rgb8*)((const uint8_t*)images + f * stride);
-}
 
 template <typename T, int BPP>
 __global__ __launch_bounds__(256) void pngw_filter_kernel(const T* __restrict__ images, long long stride, long long nimages, int w, int h, int filter,
@@ -395,21 +253,6 @@ __global__ __launch_bounds__(256) void pngw_lengths_kernel(const uint32_t* __res
 
 // ---------------------------------------------------------------------------------------------------- bit offsets
 
-struct Slot {  // where an image's DEFLATE stream goes: 32-bit words from the 4-byte boundary at or below byte 43 of the file
-  uint8_t* stream;
-  uint32_t* words;
-  uint32_t shift;
-};
-
-__device__ __forceinline__ Slot slot_of(uint8_t* out, long long slot_bytes, long long f) {
-  Slot s;
-  s.stream = out + f * slot_bytes + kStreamAt;
-  const uint32_t mis = (uint32_t)((uintptr_t)s.stream & 3);
-  s.words = (uint32_t*)(s.stream - mis);
-  s.shift = 8 * mis;
-  return s;
-}
-
 __device__ __forceinline__ uint32_t unit_bits(const uint4 v, int valid, const uint8_t* __restrict__ lens) {
   const uint32_t d[4] = {v.x, v.y, v.z, v.w};
   uint32_t bits = 0;
@@ -422,52 +265,16 @@ __global__ __launch_bounds__(1024) void pngw_scan_kernel(long long nimages, long
                                                          const uint32_t* __restrict__ tab, unsigned long long* __restrict__ offsets, uint8_t* out,
                                                          long long slot_bytes) {
   __shared__ uint8_t lens[260];
-  __shared__ uint32_t wave_total[16];
-  __shared__ unsigned long long carry_s;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const long long nunits = (F + 15) >> 4;
   for (long long f = blockIdx.x; f < nimages; f += gridDim.x) {
     const uint32_t* __restrict__ tb = tab + f * kTabWords;
     if (tb[kMeta]) continue;  // stored: nothing is packed
     __syncthreads();
     if (t < kLit) lens[t] = (uint8_t)(tb[t] >> 16);
-    const Slot sl = slot_of(out, slot_bytes, f);
-    const unsigned long long start = (unsigned long long)sl.shift + tb[kMeta + 1];
-    for (long long wd = t; wd < (long long)((start + 31) >> 5); wd += 1024) sl.words[wd] = 0;
-    if (t == 0) carry_s = start;
-    __syncthreads();
     const uint4* __restrict__ src = (const uint4*)(filt + f * filt_stride);
-    unsigned long long* __restrict__ off = offsets + f * nunits;
-    for (long long first = 0; first < nunits; first += 1024) {
-      const long long u = first + t;
-      uint32_t bits = 0;
-      if (u < nunits) {
-        const long long rem = F - u * 16;
-        bits = unit_bits(src[u], rem < 16 ? (int)rem : 16, lens);
-      }
-      uint32_t inc = bits;  // inclusive scan inside the wave: at most 1024 * 240
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t other = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += other;
-      }
-      if (lane == 63) wave_total[wave] = inc;
-      __syncthreads();
-      unsigned long long before = carry_s;
-      for (int k = 0; k < wave; k++) before += wave_total[k];
-      const unsigned long long at = before + inc - bits;
-      if (u < nunits) {
-        off[u] = at;
-        for (unsigned long long wd = (at + 31) >> 5; wd < ((at + bits + 31) >> 5); wd++) sl.words[wd] = 0;
-      }
-      __syncthreads();
-      if (t == 1023) carry_s = before + inc;
-      __syncthreads();
-    }
-    if (t == 0) {  // the end-of-block code
-      const unsigned long long at = carry_s;
-      for (unsigned long long wd = (at + 31) >> 5; wd < ((at + lens[256] + 31) >> 5); wd++) sl.words[wd] = 0;
-    }
+    scan_units(slot_of(out, slot_bytes, f), tb[kMeta + 1], F, offsets + f * nunits, lens,
+               [&](long long u, int valid) { return unit_bits(src[u], valid, lens); });
   }
 }
 
@@ -511,21 +318,8 @@ __global__ __launch_bounds__(256) void pngw_pack_kernel(long long nimages, long 
     const uint32_t* __restrict__ tb = tab + f * kTabWords;
     const uint8_t* __restrict__ src = filt + f * filt_stride;
     const Slot sl = slot_of(out, slot_bytes, f);
-    if (tb[kMeta]) {  // stored blocks: byte idx of the stream is header byte r < 5 or data byte r - 5 of block idx / 65540
-      const long long total = stored_bytes(F);
-      const int last = (int)((F - 1) / 65535);
-      for (long long idx = (long long)p * 256 + t; idx < total; idx += (long long)parts * 256) {
-        const int b = (int)(idx / 65540), r = (int)(idx - (long long)b * 65540);
-        uint8_t v;
-        if (r >= 5) {
-          v = src[(long long)b * 65535 + (r - 5)];
-        } else {
-          const long long left = F - (long long)b * 65535;
-          const uint32_t len = left < 65535 ? (uint32_t)left : 65535u;
-          v = r == 0 ? (uint8_t)(b == last) : r == 1 ? (uint8_t)len : r == 2 ? (uint8_t)(len >> 8) : r == 3 ? (uint8_t)~len : (uint8_t)(~len >> 8);
-        }
-        sl.stream[idx] = v;
-      }
+    if (tb[kMeta]) {
+      pack_stored(sl, src, F, p, parts, t);
       continue;
     }
     __syncthreads();
@@ -534,7 +328,7 @@ __global__ __launch_bounds__(256) void pngw_pack_kernel(long long nimages, long 
     if (p == 0) {
       const uint32_t hdr_bits = tb[kMeta + 1];
       for (uint32_t j = t; j < ((hdr_bits + 31) >> 5); j += 256) {
-        const uint32_t v = tb[260 + j];
+        const uint32_t v = tb[kHdrAt + j];
         if (v << sl.shift) atomicOr(sl.words + j, v << sl.shift);
         if (sl.shift && (v >> (32 - sl.shift))) atomicOr(sl.words + j + 1, v >> (32 - sl.shift));
       }
@@ -561,94 +355,23 @@ __global__ __launch_bounds__(256) void pngw_pack_kernel(long long nimages, long 
   }
 }
 
-// head: 33 bytes (signature, IHDR with its CRC) and the 12 of IEND
 __global__ __launch_bounds__(256) void pngw_finish_kernel(long long nimages, long long F, const uint8_t* __restrict__ head, const uint32_t* __restrict__ zeroed,
                                                           const uint32_t* __restrict__ tab, uint8_t* out, long long slot_bytes, int32_t* __restrict__ sizes,
                                                           int32_t* __restrict__ crc_len) {
-  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nimages; f += (long long)gridDim.x * 256) {
-    uint8_t* __restrict__ o = out + f * slot_bytes;
-    const uint32_t stream = tab[f * kTabWords + kMeta + 2];
-    const uint32_t idat = 2 + stream + 4;
-    for (int i = 0; i < 33; i++) o[i] = head[i];
-    for (int i = 0; i < 4; i++) o[33 + i] = (uint8_t)(idat >> (24 - 8 * i));
-    o[37] = 'I', o[38] = 'D', o[39] = 'A', o[40] = 'T', o[41] = 0x78, o[42] = 0x01;
-    const unsigned long long* __restrict__ sums = (const unsigned long long*)(zeroed + f * kZeroWords + kMaxSym);
-    const uint32_t s1 = (uint32_t)((1 + sums[0]) % kAdlerMod), s2 = (uint32_t)(((unsigned long long)F + sums[1]) % kAdlerMod);
-    const uint32_t adler = (s2 << 16) | s1;
-    uint8_t* __restrict__ e = o + kStreamAt + stream;
-    for (int i = 0; i < 4; i++) e[i] = (uint8_t)(adler >> (24 - 8 * i));
-    for (int i = 0; i < 12; i++) e[8 + i] = head[33 + i];
-    sizes[f] = (int32_t)(57 + 6 + stream);
-    crc_len[f] = (int32_t)(4 + idat);
-  }
+  finish_files<Layout>(nimages, F, head, zeroed, tab, out, slot_bytes, sizes, crc_len);
 }
 
 __global__ __launch_bounds__(256) void pngw_crc_kernel(long long nimages, const uint32_t* __restrict__ tab, const uint32_t* __restrict__ crc, uint8_t* out,
                                                        long long slot_bytes) {
-  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < nimages; f += (long long)gridDim.x * 256) {
-    uint8_t* __restrict__ e = out + f * slot_bytes + kStreamAt + tab[f * kTabWords + kMeta + 2] + 4;
-    const uint32_t c = crc[f];
-    for (int i = 0; i < 4; i++) e[i] = (uint8_t)(c >> (24 - 8 * i));
-  }
+  crc_bytes<Layout>(nimages, tab, crc, out, slot_bytes);
 }
-
-// ---------------------------------------------------------------------------------------------------- host side
-
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-uint32_t crc32_host(const uint8_t* p, size_t n) {
-  uint32_t c = 0xFFFFFFFFu;
-  for (size_t i = 0; i < n; i++) {
-    c ^= p[i];
-    for (int b = 0; b < 8; b++) c = (c >> 1) ^ ((c & 1) ? 0xEDB88320u : 0u);
-  }
-  return ~c;
-}
-
-void put_be32(uint8_t* p, uint32_t v) {
-  p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v;
-}
-
-// the stored form's size for rows of 1 + w * bpp bytes; -1 past 2^31 - 1
-int64_t bound_of(int w, int h, int bpp) {
-  if (w < 1 || h < 1) return -1;
-  const int64_t row = 1 + (int64_t)w * bpp;  // < 2^33
-  if (row > INT32_MAX / (int64_t)h) return -1;
-  const int64_t bound = 57 + 6 + stored_bytes(row * h);
-  return bound > INT32_MAX ? -1 : bound;
-}
-
-int create(const char* who, int device, int w, int h, int depth, int filter, int max_images, mdcp_encoder** out);
-void destroy(mdcp_encoder* enc);
-
-int grid_for(long long items) { return (int)(items < 1 ? 1 : items > kMaxGrid ? kMaxGrid : items); }
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------- host side
+
 struct mdcp_encoder {
-  int device = -1, w = 0, h = 0, depth = 0, filter = 0, max_images = 0;  // depth: bits per pixel -- 8, 16, or 24 for 8-bit RGB
+  int device = -1, w = 0, h = 0, depth = 0, bpp = 0, filter = 0, max_images = 0;  // depth: bits per pixel -- 8, 16, or 24 for 8-bit RGB
   long long F = 0, nunits = 0;
   uint8_t* d_head = nullptr;
   uint8_t* d_filt = nullptr;
@@ -697,7 +420,7 @@ int create(const char* who, int device, int w, int h, int depth, int filter, int
   DeviceGuard dg(device);
   mdcp_encoder* e = new (std::nothrow) mdcp_encoder;
   if (!e) return fail(MDCP_ERR_NOMEM, "%s: out of host memory", who);
-  e->device = device, e->w = w, e->h = h, e->depth = depth, e->filter = filter, e->max_images = max_images;
+  e->device = device, e->w = w, e->h = h, e->depth = depth, e->bpp = depth / 8, e->filter = filter, e->max_images = max_images;
   e->F = F, e->nunits = nunits;
   const size_t n = (size_t)max_images;
   if (hipMalloc((void**)&e->d_head, 48) != hipSuccess || hipMalloc((void**)&e->d_filt, n * (size_t)nunits * 16) != hipSuccess ||
@@ -708,14 +431,8 @@ int create(const char* who, int device, int w, int h, int depth, int filter, int
     destroy(e);
     return fail(MDCP_ERR_NOMEM, "%s: could not allocate the scratch arrays of %d images of %d x %d", who, max_images, w, h);
   }
-  uint8_t head[48] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n', 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
-  put_be32(head + 16, (uint32_t)w);
-  put_be32(head + 20, (uint32_t)h);
-  head[24] = (uint8_t)(depth == 24 ? 8 : depth);
-  head[25] = depth == 24 ? 2 : 0;  // colour type: truecolour or gray; compression, filter method, interlace: 0
-  put_be32(head + 29, crc32_host(head + 12, 17));
-  const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
-  memcpy(head + 33, iend, 12);
+  uint8_t head[48];
+  png_head(head, w, h, depth == 24 ? 8 : depth, depth == 24 ? 2 : 0);  // colour type: truecolour or gray
   if (hipMemcpy(e->d_head, head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) {
     destroy(e);
     return fail(MDCP_ERR_HIP, "%s: copying the header failed", who);
@@ -747,10 +464,7 @@ int encode(const char* who, mdcp_encoder* e, const T* d_images, int64_t stride, 
   if (hipMemsetAsync(e->d_zeroed, 0, (size_t)n * kZeroWords * 4, s) != hipSuccess)
     return fail(MDCP_ERR_HIP, "%s: clearing the histograms failed: %s", who, hipGetErrorString(hipGetLastError()));
   const long long groups = ((long long)e->h + kRowsPerGroup - 1) / kRowsPerGroup;
-  long long parts = (e->nunits + 1023) / 1024;
-  if (n * parts < 1024) parts = (1024 + n - 1) / n;  // few images: still fill the device
-  if (parts > (e->nunits + 255) / 256) parts = (e->nunits + 255) / 256;
-  if (parts > 4096) parts = 4096;
+  const long long parts = pack_parts(n, e->nunits);
   pngw_filter_kernel<T, BPP><<<grid_for(n * groups), 256, 0, s>>>(d_images, (long long)stride, n, e->w, e->h, e->filter, e->d_filt, fs, e->d_zeroed);
   pngw_build_kernel<<<grid_for(n), 256, 0, s>>>(n, F, e->d_zeroed, e->d_tab);
   pngw_scan_kernel<<<grid_for(n), 1024, 0, s>>>(n, F, e->d_filt, fs, e->d_tab, e->d_offsets, d_out, (long long)slot_bytes);
@@ -762,24 +476,6 @@ int encode(const char* who, mdcp_encoder* e, const T* d_images, int64_t stride, 
     return fail(MDCP_ERR_HIP, "%s: the IDAT checksum failed: %s", who, mdcz_last_error());
   pngw_crc_kernel<<<grid_for((n + 255) / 256), 256, 0, s>>>(n, e->d_tab, e->d_crc, d_out, (long long)slot_bytes);
   if ((err = hipGetLastError()) != hipSuccess) return fail(MDCP_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
-  return MDCP_OK;
-}
-
-int output_device(const char* who, mdcp_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
-  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(MDCP_ERR_ARG, "%s: null argument", who);
-  const int64_t bound = bound_of(enc->w, enc->h, enc->depth / 8);
-  if (!enc->d_out) {
-    DeviceGuard dg(enc->device);
-    uint8_t* o = nullptr;
-    int32_t* z = nullptr;
-    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_images) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_images * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(o);
-      return fail(MDCP_ERR_NOMEM, "%s: could not allocate %d slots of %lld bytes", who, enc->max_images, (long long)bound);
-    }
-    enc->d_out = o, enc->d_sizes = z;
-  }
-  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
   return MDCP_OK;
 }
 

@@ -1,29 +1,31 @@
-// The code builder and header writer of libmdc_pnglz.so (include/mdc_pnglz.h), in plain C++: the same text runs on lane 0 of the
-// build kernel (mdc_pnglz.hip) and in the stand-alone host program tests/native/pnglz_block.cpp (under the sanitizers).  The code-length
-// rule, canonical codes and the run-length coded header are include/mdc_pngw.h's, restated here so that libmdc_pngw.so stays what it is;
-// that the two agree is tested (tests/test_pnglz.py: every file that does not take the match form equals libmdc_pngw.so's).
-#ifndef MDC_PNGLZ_BLOCK_H
-#define MDC_PNGLZ_BLOCK_H
+// The DEFLATE block builder of the device PNG encoders (include/mdc_pngw.h, include/mdc_pngw_rgb.h, include/mdc_pnglz.h), in plain
+// C++ with no HIP types: the code-length rule, canonical codes, the symbol maps and the run-length coded block header.  The same text
+// runs on one lane of pngw_build_kernel and pngw_lengths_kernel (mdc_pngw.hip: the rule, the codes and the bit writer; its Huffman-only
+// header writer is its own), on two lanes of pnglz_build_kernel (mdc_pnglz.hip) and in the stand-alone host program
+// tests/native/pnglz_block.cpp (under the sanitizers).
+#ifndef MDC_PNG_BLOCK_H
+#define MDC_PNG_BLOCK_H
 #include <stdint.h>
 
-#ifndef PNGLZ_HD
-#define PNGLZ_HD inline
+#ifndef PNG_HD
+#define PNG_HD inline
 #endif
 
-namespace pnglz {
+namespace png {
 
 constexpr int kLitLen = 286;     // literals, end-of-block, length symbols
 constexpr int kDist = 30;        // distance symbols
 constexpr int kAll = kLitLen + kDist;
 constexpr int kEob = 256;
+constexpr int kMaxSym = 288;     // the largest alphabet huff_lengths takes: MDCP_MAX_SYMBOLS of include/mdc_pngw.h
 constexpr int kHdrWords = 144;   // 17 + 57 + 316 * 14 bits at most: 141 words
 constexpr int kMinMatch = 4, kMaxMatch = 258, kWindow = 32768, kChunk = 4096;
 
 struct HuffWork {
-  unsigned long long wt[2 * kLitLen];
-  uint16_t parent[2 * kLitLen];
-  uint16_t depth[2 * kLitLen];
-  uint16_t order[kLitLen];
+  unsigned long long wt[2 * kMaxSym];
+  uint16_t parent[2 * kMaxSym];
+  uint16_t depth[2 * kMaxSym];
+  uint16_t order[kMaxSym];
   uint32_t count[16], next[16];
 };
 
@@ -43,7 +45,7 @@ struct Block {
 };
 
 // the length symbol of a match of `length` 4..258, its extra bits and their count
-PNGLZ_HD void length_symbol(int length, int& sym, int& extra, int& nextra) {
+PNG_HD void length_symbol(int length, int& sym, int& extra, int& nextra) {
   const int l = length - 3;
   if (length == kMaxMatch) {
     sym = 285, extra = 0, nextra = 0;
@@ -60,7 +62,7 @@ PNGLZ_HD void length_symbol(int length, int& sym, int& extra, int& nextra) {
 }
 
 // the distance symbol of `distance` 1..32768
-PNGLZ_HD void distance_symbol(int distance, int& sym, int& extra, int& nextra) {
+PNG_HD void distance_symbol(int distance, int& sym, int& extra, int& nextra) {
   const int d = distance - 1;
   if (d < 4) {
     sym = d, extra = 0, nextra = 0;
@@ -72,11 +74,11 @@ PNGLZ_HD void distance_symbol(int distance, int& sym, int& extra, int& nextra) {
   extra = d & ((1 << nextra) - 1);
 }
 
-PNGLZ_HD int length_extra_bits(int sym) { return (sym < 265 || sym == 285) ? 0 : (sym - 261) >> 2; }
-PNGLZ_HD int distance_extra_bits(int sym) { return sym < 4 ? 0 : (sym - 2) >> 1; }
+PNG_HD int length_extra_bits(int sym) { return (sym < 265 || sym == 285) ? 0 : (sym - 261) >> 2; }
+PNG_HD int distance_extra_bits(int sym) { return sym < 4 ? 0 : (sym - 2) >> 1; }
 
 // order[r] = the used symbol of rank r by (count, symbol); lanes tid, tid + nthr, ... of the caller take their symbols
-PNGLZ_HD void huff_order(const uint32_t* hist, int nsym, uint16_t* order, int tid, int nthr) {
+PNG_HD void huff_order(const uint32_t* hist, int nsym, uint16_t* order, int tid, int nthr) {
   for (int s = tid; s < nsym; s += nthr) {
     const uint32_t c = hist[s];
     if (!c) continue;
@@ -89,8 +91,8 @@ PNGLZ_HD void huff_order(const uint32_t* hist, int nsym, uint16_t* order, int ti
   }
 }
 
-// include/mdc_pngw.h, "Code lengths"; k.order is filled
-PNGLZ_HD void huff_lengths(const uint32_t* hist, int nsym, int limit, HuffWork& k, uint8_t* len) {
+// include/mdc_pngw.h, "Code lengths"; nsym <= kMaxSym, k.order is filled
+PNG_HD void huff_lengths(const uint32_t* hist, int nsym, int limit, HuffWork& k, uint8_t* len) {
   int n = 0;
   for (int s = 0; s < nsym; s++) {
     len[s] = 0;
@@ -133,7 +135,7 @@ PNGLZ_HD void huff_lengths(const uint32_t* hist, int nsym, int limit, HuffWork& 
         any = true;
       }
     }
-    if (!any) break;  // n > 2^limit: no alphabet here is that large
+    if (!any) break;  // n > 2^limit: refused before the launch, and no alphabet of a block is that large
   }
   while (kraft < full) {
     const uint32_t room = full - kraft;
@@ -147,7 +149,7 @@ PNGLZ_HD void huff_lengths(const uint32_t* hist, int nsym, int limit, HuffWork& 
 }
 
 // codes[s] = the canonical code of symbol s, bit-reversed, | length << 16
-PNGLZ_HD void canonical(const uint8_t* len, int nsym, int limit, HuffWork& k, uint32_t* codes) {
+PNG_HD void canonical(const uint8_t* len, int nsym, int limit, HuffWork& k, uint32_t* codes) {
   for (int b = 0; b <= limit; b++) k.count[b] = 0;
   for (int s = 0; s < nsym; s++) k.count[len[s]]++;
   k.count[0] = 0;
@@ -167,18 +169,19 @@ PNGLZ_HD void canonical(const uint8_t* len, int nsym, int limit, HuffWork& k, ui
   }
 }
 
-PNGLZ_HD void put_bits(uint32_t* words, uint32_t& nbits, uint32_t v, int n) {
+PNG_HD void put_bits(uint32_t* words, uint32_t& nbits, uint32_t v, int n) {
   const uint32_t at = nbits & 31;
   words[nbits >> 5] |= v << at;
   if (at + n > 32) words[(nbits >> 5) + 1] |= v >> (32 - at);
   nbits += n;
 }
 
-PNGLZ_HD long long stored_bytes(long long F) { return F + 5 * ((F + 65534) / 65535); }
+PNG_HD long long stored_bytes(long long F) { return F + 5 * ((F + 65534) / 65535); }
 
-// One dynamic block from the two histograms: both codes, the header and the stream's size.  With no distance symbol used this is
-// include/mdc_pngw.h's Huffman-only block bit for bit (HLIT 257 codes, one distance code of length 0).
-PNGLZ_HD void build_block(Block& B) {
+// One dynamic block from the two histograms: both codes, the header and the stream's size.  With no length and no distance symbol
+// used this is include/mdc_pngw.h's Huffman-only block bit for bit (HLIT 257 codes, one distance code of length 0), which
+// mdc_pngw.hip builds with a text of its own.
+PNG_HD void build_block(Block& B) {
   huff_lengths(B.hist, kLitLen, 15, B.work, B.len);
   canonical(B.len, kLitLen, 15, B.work, B.codes);
   huff_order(B.hist + kLitLen, kDist, B.work.order, 0, 1);
@@ -242,11 +245,11 @@ PNGLZ_HD void build_block(Block& B) {
   unsigned long long data = 0;
   for (int s = 0; s < kLitLen; s++)
     if (s != kEob) data += (unsigned long long)B.hist[s] * (unsigned)(B.len[s] + (s > kEob ? length_extra_bits(s) : 0));
-  for (int s = 0; s < kDist; s++) data += (unsigned long long)B.hist[kLitLen + s] * (unsigned)(B.len[kLitLen + s] + distance_extra_bits(s));
+  for (int s = 0; s < kDist; s++) data +=(unsigned long long)B.hist[kLitLen + s] * (unsigned)(B.len[kLitLen + s] + distance_extra_bits(s));
   B.hdr_bits = bits;
   B.data_bits = data;
   B.bytes = (long long)((bits + data + B.len[kEob] + 7) >> 3);
 }
 
-}  // namespace pnglz
-#endif  // MDC_PNGLZ_BLOCK_H
+}  // namespace png
+#endif  // MDC_PNG_BLOCK_H

@@ -2,7 +2,8 @@
 inflates every restated IDAT to the filtered bytes and PIL reads every file back to the pixels; the token invariants; the files
 that take no match are the Huffman-only restatement's, and none is larger; the smooth frame's ratio; header, library and ctypes
 table are one set; the argument errors come without a device; the kernels' scratch, register and LDS budgets; and the code builder
-as a stand-alone host program under the sanitizers, against the restatement on directed histograms."""
+(csrc/png_block.h, shared with libmdc_pngw.so) as a stand-alone host program under the sanitizers, against the restatements on directed
+histograms: the blocks, the block without matches against libmdc_pngw.so's restatement, and the code lengths of alphabets up to 288 symbols."""
 import ctypes
 import io
 import os
@@ -133,7 +134,7 @@ def test_library_links_the_zip_writer_only_and_only_the_program_links_it():
     undefined = subprocess.run(["nm", "-D", "--undefined-only", build.LIB_PNGLZ], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert sorted(w for w in undefined.split() if w.startswith("mdc")) == ["mdcz_crc32_device", "mdcz_last_error"]
     assert "libmdc_pnglz.so" in subprocess.run(["readelf", "-d", build.RECTIFY_DATASET], stdout=subprocess.PIPE, text=True, check=True).stdout
-    for f in (build.PNGLZ_SOURCE, build.PNGLZ_BLOCK, build.PNGLZ_EXPORT_MAP, os.path.join(ROOT, "include", "mdc_pnglz.h")):
+    for f in (build.PNGLZ_SOURCE, build.PNG_BLOCK, build.PNG_ENCODE_CORE, build.PNGLZ_EXPORT_MAP, os.path.join(ROOT, "include", "mdc_pnglz.h")):
         assert os.path.exists(f) and f not in set(build.HIP_DEPS) | set(build.HOST_DEPS), f
 
 
@@ -261,3 +262,37 @@ def test_code_builder_as_a_host_program_under_the_sanitizers(tmp_path):
         assert [int(v) for v in sizes] == [bits.n, (bits.n + data + ll_len[256] + 7) // 8, data], name
         assert int.from_bytes(b"".join(int(w, 16).to_bytes(4, "little") for w in words), "little") == bits.value, name
         assert max(ll_len + d_len) <= 15
+        if name == "no_distance":  # libmdc_pngw.so's block: HLIT = 0 (257 codes), HDIST = 0 (one code), the Huffman-only restatement's header
+            assert not any(ll[257:]) and not any(d)
+            assert (bits.value >> 3) & 0x3ff == 0
+            stream, lit_len = P.dynamic_block(bytes(np.repeat(np.arange(256, dtype=np.uint8), ll[:256])))
+            assert lit_len == ll_len[:257] and len(stream) == int(sizes[1])
+            assert int.from_bytes(stream, "little") & ((1 << bits.n) - 1) == bits.value
+
+
+def lengths_cases():
+    """(name, counts, limit): every alphabet size up to the work area's 288 entries, and the code-length alphabet; all equal, Fibonacci
+    counts in the last symbols (clamping Huffman's depths to the limit fails the Kraft sum: the repair loops run), one used symbol"""
+    out = []
+    for nsym, limit in ((286, 15), (287, 15), (288, 15), (19, 7)):
+        fib = P.fibonacci(min(nsym, 40))
+        out.append(("equal_%d" % nsym, [5] * nsym, limit))
+        out.append(("fibonacci_%d" % nsym, [0] * (nsym - len(fib)) + fib, limit))
+        out.append(("one_symbol_%d" % nsym, [0] * (nsym - 1) + [7], limit))
+    return out
+
+
+def test_code_lengths_as_a_host_program_up_to_288_symbols(tmp_path):
+    from mono_dataset_code_amd import build
+
+    exe = build.build_pnglz_block_program(str(tmp_path / "pnglz_block"))
+    cases = lengths_cases()
+    text = "".join("%d %d %s\n" % (len(h), limit, " ".join(str(v) for v in h)) for _, h, limit in cases)
+    r = subprocess.run([exe, "lengths"], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(cases)
+    for (name, h, limit), line in zip(cases, lines):
+        assert [int(v) for v in line.split()] == P.huffman_lengths(h, limit), name
+        if name.startswith("fibonacci"):  # the limit is active
+            assert max(int(v) for v in line.split()) == limit, name

@@ -190,7 +190,7 @@ def test_product_build_identity_is_unchanged():
 
     assert build.code_id() == json.load(open(os.path.join(ROOT, "profiles", "r06_fused_summary.json")))["code_id"]
     deps = set(build.HIP_DEPS) | set(build.HOST_DEPS)
-    for f in (build.PNGW_SOURCE, build.PNGW_EXPORT_MAP, os.path.join(ROOT, "include", "mdc_pngw.h")):
+    for f in (build.PNGW_SOURCE, build.PNG_BLOCK, build.PNG_ENCODE_CORE, build.PNGW_EXPORT_MAP, os.path.join(ROOT, "include", "mdc_pngw.h")):
         assert os.path.exists(f) and f not in deps, f
 
 
