@@ -37,34 +37,45 @@ def distance_symbol(dist):
     return k, dist - DIST_BASE[k][0], DIST_BASE[k][1]
 
 
-def tokens(data, chain):
+def order_and_rank(data):
+    """-> (key, order, rank) of the positions p with p + 2 < F: key[p] the trigram as a number, order the positions "by trigram, then
+    by position", rank its inverse (rank[order[i]] = i): the candidates of p are order[rank[p] - 1], order[rank[p] - 2], ..."""
+    d = np.frombuffer(bytes(data), np.uint8)
+    n = max(len(d) - 2, 0)
+    key = (d[:n].astype(np.int64) << 16) | (d[1:n + 1].astype(np.int64) << 8) | d[2:n + 2]
+    order = np.argsort(key, kind="stable")
+    rank = np.empty(n, np.int64)
+    rank[order] = np.arange(n)
+    return key, order, rank
+
+
+def tokens(data, chain, *, window=WINDOW, max_match=MAX_MATCH, chunk=CHUNK, candidate=None, length_of=None):
     """-> [(position, length, distance)]: length 1 and distance 0 for a literal.  The candidates of p are its up to `chain`
-    predecessors in the order "by trigram, then by position", as long as they share its trigram and lie within the window."""
+    predecessors in the order "by trigram, then by position", as long as they share its trigram and lie within the window.
+    The keyword arguments are for tests that restate a wrong encoder, and their defaults are the header's rule: candidate(r, k) says
+    whether the position of rank r may look at rank r - k (False ends its search), length_of(length, cap) replaces a common length."""
     assert 1 <= chain <= MAX_CHAIN
     d = np.frombuffer(bytes(data), np.uint8)
     F = len(d)
     n = max(F - 2, 0)
     if n:
-        key = (d[:n].astype(np.int64) << 16) | (d[1:n + 1].astype(np.int64) << 8) | d[2:n + 2]
-        order = np.argsort(key, kind="stable")
-        rank = np.empty(n, np.int64)
-        rank[order] = np.arange(n)
+        key, order, rank = order_and_rank(data)
         order_l, key_l = order.tolist(), key.tolist()
     raw = bytes(data)
     out, p = [], 0
-    for start in range(0, F, CHUNK):
-        end = min(F, start + CHUNK)
+    for start in range(0, F, chunk):
+        end = min(F, start + chunk)
         p = start
         while p < end:
             best, best_dist = 0, 0
-            cap = min(MAX_MATCH, F - p, CHUNK - p % CHUNK)
+            cap = min(max_match, F - p, chunk - p % chunk)
             if p + 2 < F and cap >= MIN_MATCH:
                 r = int(rank[p])
                 for k in range(1, chain + 1):
-                    if r - k < 0:
+                    if r - k < 0 or (candidate is not None and not candidate(r, k)):
                         break
                     q = order_l[r - k]
-                    if key_l[q] != key_l[p] or p - q > WINDOW:
+                    if key_l[q] != key_l[p] or p - q > window:
                         break
                     assert q < p
                     if raw[q + 3] != raw[p + 3]:
@@ -72,6 +83,8 @@ def tokens(data, chain):
                     a, b = d[q:q + cap], d[p:p + cap]
                     diff = np.flatnonzero(a != b)
                     length = int(diff[0]) if diff.size else cap
+                    if length_of is not None:
+                        length = length_of(length, cap)
                     if length > best:  # of equal lengths the nearest, which came first
                         best, best_dist = length, p - q
                     if best == cap:
@@ -153,10 +166,10 @@ def match_block(data, toks):
     return np.packbits(stream, bitorder="little").tobytes()
 
 
-def deflate(data, chain):
-    """-> (the DEFLATE stream, the form, tokens, matches, L): the choice of form of the header"""
+def deflate(data, chain, **wrong):
+    """-> (the DEFLATE stream, the form, tokens, matches, L): the choice of form of the header (wrong: see tokens)"""
     data = bytes(data)
-    toks = tokens(data, chain)
+    toks = tokens(data, chain, **wrong)
     nmatch = sum(1 for t in toks if t[2])
     with_matches = match_block(data, toks)
     huffman, _ = P.dynamic_block(data)
@@ -176,12 +189,12 @@ def filtered(img, kind, filt):
     return P.filtered(img, 16 if kind == GRAY16 else 8, filt)
 
 
-def encode(img, kind, filt, chain):
-    """-> (the file, (form, tokens, matches, L))"""
+def encode(img, kind, filt, chain, **wrong):
+    """-> (the file, (form, tokens, matches, L)); wrong: see tokens"""
     img = np.asarray(img)
     h, w = img.shape[:2]
     data = filtered(img, kind, filt).tobytes()
-    stream, form, ntok, nmatch, L = deflate(data, chain)
+    stream, form, ntok, nmatch, L = deflate(data, chain, **wrong)
     idat = b"\x78\x01" + stream + struct.pack(">I", zlib.adler32(data))
     ihdr = struct.pack(">IIBBBBB", w, h, 16 if kind == GRAY16 else 8, 2 if kind == RGB8 else 0, 0, 0, 0)
     out = P.SIGNATURE + P.chunk(b"IHDR", ihdr) + struct.pack(">I", len(idat)) + b"IDAT" + idat + struct.pack(">I", zlib.crc32(b"IDAT" + idat)) + P.chunk(b"IEND", b"")
