@@ -207,9 +207,10 @@ def build_programs(force=False):
     libmdc_pngw_rgb.so for its result images;
     bin/playDataset: its playDataset program in the saving mode, on top of those and libmdc_jenc.so;
     bin/rectifyDataset: a sequence rectified into a dataset folder (images.zip, camera.txt, ...), on top of those, libmdc_zipw.so,
-    libmdc_pngw.so and libmdc_pnglz.so."""
+    libmdc_pngw.so, libmdc_pnglz.so and libmdc_jopt.so."""
     build_host(force)
     build_jenc(force)
+    build_jopt(force)
     build_zipw(force)
     build_pngw(force)
     build_pngw_rgb(force)
@@ -227,11 +228,12 @@ def build_programs(force=False):
     if force or _stale(PLAY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
               PLAY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-Wl,-rpath,$ORIGIN/..", "-o", PLAY_DATASET])
-    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_ZIPW, LIB_PNGW, LIB_PNGLZ, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
+    deps = [RECTIFY_DATASET_SOURCE, LIB_HOST, LIB_HIP, LIB_JENC, LIB_JOPT, LIB_ZIPW, LIB_PNGW, LIB_PNGLZ, os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_jenc.h"),
+            os.path.join(INC, "mdc_jopt.h"),
             os.path.join(INC, "mdc_zipw.h"), os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h")]
     if force or _stale(RECTIFY_DATASET, deps):
         _run(["g++", "-O2", "-std=c++11", "-Wall", "-I" + INC, "-I" + os.path.join(INC, "mono_dataset_code"), "-I" + eigen_include(),
-              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_zipw", "-lmdc_pngw", "-lmdc_pnglz", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
+              RECTIFY_DATASET_SOURCE, "-L" + PKG, "-lmdc_host", "-lmdc_hip", "-lmdc_jenc", "-lmdc_jopt", "-lmdc_zipw", "-lmdc_pngw", "-lmdc_pnglz", "-Wl,-rpath,$ORIGIN/..", "-o", RECTIFY_DATASET])
     return RESPONSE_CALIB
 
 
@@ -250,15 +252,40 @@ def build_bench(force=False):
 LIB_JENC = os.path.join(PKG, "libmdc_jenc.so")
 JENC_SOURCE = os.path.join(CSRC, "mdc_jenc.hip")
 JENC_EXPORT_MAP = os.path.join(CSRC, "mdc_jenc_exports.map")
+JPEG_ENCODE_CORE = os.path.join(CSRC, "jpeg_encode_core.h")  # what the two JPEG encoder libraries share: tables, DCT, block walker, scan, host helpers
 
 
 def build_jenc(force=False):
     """libmdc_jenc.so: the device baseline JPEG encoder (include/mdc_jenc.h) -- one translation unit, independent of libmdc_hip.so
     and outside its build identity."""
-    if force or _stale(LIB_JENC, [JENC_SOURCE, os.path.join(INC, "mdc_jenc.h"), JENC_EXPORT_MAP]):
+    if force or _stale(LIB_JENC, [JENC_SOURCE, JPEG_ENCODE_CORE, os.path.join(INC, "mdc_jenc.h"), JENC_EXPORT_MAP]):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, JENC_SOURCE, "-Wl,--version-script=" + JENC_EXPORT_MAP, "-o", LIB_JENC])
     return LIB_JENC
+
+
+LIB_JOPT = os.path.join(PKG, "libmdc_jopt.so")
+JOPT_SOURCE = os.path.join(CSRC, "mdc_jopt.hip")
+JOPT_EXPORT_MAP = os.path.join(CSRC, "mdc_jopt_exports.map")
+JOPT_TABLE = os.path.join(CSRC, "jpeg_optimal_table.h")  # the table rule, plain C++: libmdc_jopt.so and a CPU test program
+
+
+def build_jopt(force=False):
+    """libmdc_jopt.so: the device JPEG encoder with per-frame optimal Huffman tables (include/mdc_jopt.h) -- one translation unit,
+    the header it shares with mdc_jenc.hip and the table rule's header; it links neither libmdc_jenc.so nor libmdc_hip.so and is
+    outside the product's build identity."""
+    if force or _stale(LIB_JOPT, [JOPT_SOURCE, JPEG_ENCODE_CORE, JOPT_TABLE, os.path.join(INC, "mdc_jopt.h"), JOPT_EXPORT_MAP]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, JOPT_SOURCE, "-Wl,--version-script=" + JOPT_EXPORT_MAP, "-o", LIB_JOPT])
+    return LIB_JOPT
+
+
+def build_jopt_table_program(out, sanitize=True):
+    """tests/native/jopt_table.cpp: csrc/jpeg_optimal_table.h (the table rule of libmdc_jopt.so) as a stand-alone program, under
+    AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_jopt_cpu.py).  Pure host code."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "jopt_table.cpp"), "-o", out])
+    return out
 
 
 LIB_ZIPW = os.path.join(PKG, "libmdc_zipw.so")
@@ -427,6 +454,7 @@ def build_all(force=False):
     build_multi(force)
     build_bench(force)
     build_jenc(force)
+    build_jopt(force)
     build_zipw(force)
     build_pngw(force)
     build_pngw_rgb(force)

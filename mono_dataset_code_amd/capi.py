@@ -289,6 +289,19 @@ JENC_API = {  # include/mdc_jenc.h (libmdc_jenc.so: the device JPEG encoder, a l
     "mdcj_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
     "mdcj_fetch": (_i64, [_vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
 }
+JOPT_API = {  # include/mdc_jopt.h (libmdc_jopt.so: the JPEG encoder with per-frame optimal Huffman tables, a library of its own)
+    "mdcjo_jpeg_bound": (_i64, [_i, _i]),
+    "mdcjo_last_error": (_cp, []),
+    "mdcjo_create": (_i, [_i, _i, _i, _i, _i, _P(_vp)]),
+    "mdcjo_destroy": (None, [_vp]),
+    "mdcjo_encode_f32_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcjo_encode_u8_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "mdcjo_output_device": (_i, [_vp, _P(_vp), _P(_i64), _P(_vp)]),
+    "mdcjo_fetch": (_i64, [_vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
+    "mdcjo_optimal_tables_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mdcjo_profile": (_i, [_vp, _i]),
+    "mdcjo_kernel_ms": (_i, [_vp, _P(_f)]),
+}
 ZIPW_API = {  # include/mdc_zipw.h (libmdc_zipw.so: ZIP archives of device-resident files, a library of its own)
     "mdcz_last_error": (_cp, []),
     "mdcz_crc_geometry": (None, [_i64, _i64, _P(_i64)]),
@@ -351,6 +364,7 @@ HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(B
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
 LIB_JENC_PATH = os.path.join(_PKG, "libmdc_jenc.so")
+LIB_JOPT_PATH = os.path.join(_PKG, "libmdc_jopt.so")
 LIB_ZIPW_PATH = os.path.join(_PKG, "libmdc_zipw.so")
 LIB_PNGW_PATH = os.path.join(_PKG, "libmdc_pngw.so")
 LIB_PNGW_RGB_PATH = os.path.join(_PKG, "libmdc_pngw_rgb.so")
@@ -360,6 +374,7 @@ _hip = None
 _host = None
 _bench = None
 _jenc = None
+_jopt = None
 _zipw = None
 _pngw = None
 _pngw_rgb = None
@@ -418,6 +433,15 @@ def jenc_lib():
         _share_hip_runtime_with_torch()
         _jenc = _load(LIB_JENC_PATH, JENC_API)
     return _jenc
+
+
+def jopt_lib():
+    """libmdc_jopt.so: the JPEG encoder with one optimal Huffman table pair per frame (include/mdc_jopt.h)."""
+    global _jopt
+    if _jopt is None:
+        _share_hip_runtime_with_torch()
+        _jopt = _load(LIB_JOPT_PATH, JOPT_API)
+    return _jopt
 
 
 def zipw_lib():
@@ -1163,27 +1187,36 @@ class PhotometricUndistorter:
 
 class JpegEncoder:
     """One mdcj_encoder (include/mdc_jenc.h): device-resident w x h frames -> one baseline JFIF file per frame, the bytes
-    libjpeg writes at `quality`.  encode() fills device slots (the encoder's own unless d_out / d_sizes are given) and returns
-    (d_out, sizes); files() brings the encoded bytes, and only those, to the host."""
+    libjpeg writes at `quality`.  huffman="optimal" takes libmdc_jopt.so instead (include/mdc_jopt.h: one Huffman table pair per
+    frame, the smaller file libjpeg writes with optimize_coding; the same pixels); "standard", the default, is the Annex K tables.
+    encode() fills device slots (the encoder's own unless d_out / d_sizes are given) and returns (d_out, sizes); files() brings
+    the encoded bytes, and only those, to the host."""
 
-    def __init__(self, w, h, quality=95, max_frames=1, device=-1):
-        self._L = jenc_lib()
+    def __init__(self, w, h, quality=95, max_frames=1, device=-1, huffman="standard"):
+        if huffman not in ("standard", "optimal"):
+            raise MdcError(ERR_ARG, "JpegEncoder: huffman %r is neither 'standard' nor 'optimal'" % (huffman,))
+        self.huffman = huffman
+        self._L = jopt_lib() if huffman == "optimal" else jenc_lib()
+        self._prefix = "mdcjo_" if huffman == "optimal" else "mdcj_"
         self.w, self.h, self.quality, self.max_frames = int(w), int(h), int(quality), int(max_frames)
         h_ = _vp()
-        self._check(self._L.mdcj_create(int(device), self.w, self.h, self.quality, self.max_frames, C.byref(h_)))
+        self._check(self._fn("create")(int(device), self.w, self.h, self.quality, self.max_frames, C.byref(h_)))
         self._h = h_
-        self.bound = int(self._L.mdcj_jpeg_bound(self.w, self.h))
+        self.bound = int(self._fn("jpeg_bound")(self.w, self.h))
         self._own = None
         self._last = None
 
+    def _fn(self, name):
+        return getattr(self._L, self._prefix + name)
+
     def _check(self, rc):
         if rc < 0:
-            raise MdcError(int(rc), self._L.mdcj_last_error().decode())
+            raise MdcError(int(rc), self._fn("last_error")().decode())
         return rc
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.mdcj_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     __del__ = close
@@ -1192,7 +1225,7 @@ class JpegEncoder:
         """(d_out, slot_bytes, d_sizes): the encoder's own output arrays, max_frames slots of `bound` bytes"""
         if self._own is None:
             o, n, z = _vp(), _i64(), _vp()
-            self._check(self._L.mdcj_output_device(self._h, C.byref(o), C.byref(n), C.byref(z)))
+            self._check(self._fn("output_device")(self._h, C.byref(o), C.byref(n), C.byref(z)))
             self._own = (o.value, n.value, z.value)
         return self._own
 
@@ -1201,11 +1234,11 @@ class JpegEncoder:
         -> (d_out, sizes): the device address of the slots (slot_bytes apart) and the files' lengths as a numpy array."""
         if d_out is None:
             d_out, slot_bytes, d_sizes = self.output()
-        fn = self._L.mdcj_encode_u8_device if u8 else self._L.mdcj_encode_f32_device
+        fn = self._fn("encode_u8_device" if u8 else "encode_f32_device")
         stride = self.w * self.h if frame_stride is None else int(frame_stride)
         self._check(fn(self._h, d_frames, stride, int(nframes), d_out, int(slot_bytes), d_sizes, _stream(stream)))
         sizes = np.zeros(int(nframes), np.int32)
-        self._check(self._L.mdcj_fetch(self._h, d_out, int(slot_bytes), d_sizes, int(nframes), None, 0, _np_ptr(sizes), _stream(stream)))
+        self._check(self._fn("fetch")(self._h, d_out, int(slot_bytes), d_sizes, int(nframes), None, 0, _np_ptr(sizes), _stream(stream)))
         self._last = (d_out, int(slot_bytes), d_sizes, int(nframes), stream)
         return d_out, sizes
 
@@ -1214,12 +1247,31 @@ class JpegEncoder:
         if self._last is None:
             raise MdcError(ERR_STATE, "JpegEncoder.files: nothing has been encoded")
         d_out, slot_bytes, d_sizes, nframes, stream = self._last
+        fetch = self._fn("fetch")
         sizes = np.zeros(nframes, np.int32)
-        total = self._check(self._L.mdcj_fetch(self._h, d_out, slot_bytes, d_sizes, nframes, None, 0, _np_ptr(sizes), _stream(stream)))
+        total = self._check(fetch(self._h, d_out, slot_bytes, d_sizes, nframes, None, 0, _np_ptr(sizes), _stream(stream)))
         buf = np.zeros(max(int(total), 1), np.uint8)
-        self._check(self._L.mdcj_fetch(self._h, d_out, slot_bytes, d_sizes, nframes, _np_ptr(buf), buf.size, _np_ptr(sizes), _stream(stream)))
+        self._check(fetch(self._h, d_out, slot_bytes, d_sizes, nframes, _np_ptr(buf), buf.size, _np_ptr(sizes), _stream(stream)))
         at = np.concatenate([[0], np.cumsum(sizes)])
         return [buf[at[i]:at[i + 1]].tobytes() for i in range(nframes)]
+
+    def optimal_tables(self, freq, stream=0):
+        """huffman="optimal" only: mdcjo_optimal_tables_device on `freq` (ntables x 257 counts, host) -> (bits ntables x 16, vals
+        ntables x 256, nvals, status) as numpy arrays; the histograms and results travel through device memory of this call."""
+        if self.huffman != "optimal":
+            raise MdcError(ERR_STATE, "JpegEncoder.optimal_tables: the encoder was made with huffman='standard'")
+        import torch
+
+        freq = np.ascontiguousarray(freq, np.uint32).reshape(-1, 257)
+        n = freq.shape[0]
+        dev = "cuda:%d" % torch.cuda.current_device()
+        d_freq = torch.from_numpy(freq.view(np.int32)).to(dev)
+        d_bits, d_vals = torch.zeros(n * 16, dtype=torch.uint8, device=dev), torch.zeros(n * 256, dtype=torch.uint8, device=dev)
+        d_nvals, d_status = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev)
+        self._check(self._L.mdcjo_optimal_tables_device(self._h, d_freq.data_ptr(), n, d_bits.data_ptr(), d_vals.data_ptr(), d_nvals.data_ptr(),
+                                                        d_status.data_ptr(), _stream(stream)))
+        torch.cuda.synchronize()
+        return d_bits.cpu().numpy().reshape(n, 16), d_vals.cpu().numpy().reshape(n, 256), d_nvals.cpu().numpy(), d_status.cpu().numpy()
 
 
 PNG_FILTER_ADAPTIVE = 5  # MDCP_FILTER_ADAPTIVE

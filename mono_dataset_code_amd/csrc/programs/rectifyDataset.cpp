@@ -1,5 +1,5 @@
-// rectifyDataset <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1] [compress=huffman|lz77] [chain=N]: a sequence,
-// rectified, as a dataset
+// rectifyDataset <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1] [compress=huffman|lz77] [chain=N]
+// [huffman=standard|optimal]: a sequence, rectified, as a dataset
 // of its own.  The key=value arguments may stand in any position behind the two folders; a bare number is the JPEG quality.
 // The frames are those of playDataset's saving mode -- getImage(i, true, false, false, false), encoded by include/mdc_jenc.h with the
 // bytes cv::imwrite gives a CV_32F image -- but they go into one images.zip of stored %05d.jpg entries, built on the device by
@@ -15,6 +15,9 @@
 // include/mdc_pnglz.h instead: the same pixels in files that are never larger.  Such files carry distance codes, which the reader
 // decodes on the host unless MDC_GPU_PNG=2 sends them to the device decoder's general path.  The default, compress=huffman, writes
 // today's files byte for byte.  A bad value is refused with one line before anything is opened or created.
+// huffman=optimal (with frames=jpg only) encodes the frames by include/mdc_jopt.h instead: one Huffman table pair per frame, the file
+// libjpeg writes with optimize_coding (PIL: optimize=True) -- the same pixels in smaller files.  The default, huffman=standard, is the
+// Annex K tables: today's files byte for byte.
 // vignette.png is NOT exported by default, and the exported dataset then opens with validVignette == false, as any dataset without
 // that file does.  vignette=1 writes <out>/vignette.png, 16-bit, if the source has a valid vignette (one line says so if not):
 //   V = the source's vignetteMap (normalised to a maximum of 1; not the inverse);  R = undistort<float>(V) through the sequence's
@@ -42,6 +45,7 @@
 #include "mdc_hip.h"
 #include "mdc_host.h"
 #include "mdc_jenc.h"
+#include "mdc_jopt.h"
 #include "mdc_pnglz.h"
 #include "mdc_pngw.h"
 #include "mdc_zipw.h"
@@ -144,20 +148,25 @@ static int export_vignette(DatasetReader* reader, const std::string& dataset, co
 }
 
 int main(int argc, char** argv) {
-  const char* usage = "usage: %s <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1] [compress=huffman|lz77] [chain=N]\n";
+  const char* usage = "usage: %s <dataset folder> <output folder> [quality=95] [frames=jpg|png] [vignette=0|1] [compress=huffman|lz77] [chain=N] [huffman=standard|optimal]\n";
   if (argc < 3) {
     fprintf(stderr, usage, argv[0]);
     return 1;
   }
   std::string dataset = argv[1], out = argv[2];
   int quality = 95;
-  bool png = false, vignette = false, lz77 = false, chain_given = false;
+  bool png = false, vignette = false, lz77 = false, chain_given = false, optimal = false;
   int chain = 4;
   for (int i = 3; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "frames=png" || a == "frames=jpg") png = a == "frames=png";
     else if (a == "vignette=1" || a == "vignette=0") vignette = a == "vignette=1";
     else if (a == "compress=huffman" || a == "compress=lz77") lz77 = a == "compress=lz77";
+    else if (a == "huffman=standard" || a == "huffman=optimal") optimal = a == "huffman=optimal";
+    else if (a.compare(0, 8, "huffman=") == 0) {
+      fprintf(stderr, "rectifyDataset: %s: huffman is standard or optimal\n", argv[i]);
+      return 1;
+    }
     else if (a.compare(0, 6, "chain=") == 0) {
       char* end = 0;
       const long v = strtol(a.c_str() + 6, &end, 10);
@@ -182,6 +191,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "rectifyDataset: compress=lz77 needs frames=png\n");
     return 1;
   }
+  if (optimal && png) {
+    fprintf(stderr, "rectifyDataset: huffman=optimal needs frames=jpg\n");
+    fprintf(stderr, usage, argv[0]);
+    return 1;
+  }
   if (chain_given && !lz77) {
     fprintf(stderr, "rectifyDataset: chain=%d needs compress=lz77\n", chain);
     return 1;
@@ -204,11 +218,13 @@ int main(int argc, char** argv) {
   }
   if (lz77) printf("Rectifying %s: %d frames of %d x %d into %s (PNG, 8-bit, lossless, LZ77 matches of depth %d)\n", dataset.c_str(), total, w, h, out.c_str(), chain);
   else if (png) printf("Rectifying %s: %d frames of %d x %d into %s (PNG, 8-bit, lossless)\n", dataset.c_str(), total, w, h, out.c_str());
+  else if (optimal) printf("Rectifying %s: %d frames of %d x %d into %s (JPEG quality %d, optimal Huffman tables)\n", dataset.c_str(), total, w, h, out.c_str(), quality);
   else printf("Rectifying %s: %d frames of %d x %d into %s (JPEG quality %d)\n", dataset.c_str(), total, w, h, out.c_str(), quality);
 
   const int chunk = total < 128 ? (total > 0 ? total : 1) : 128;
   const size_t frame = (size_t)w * h;
   mdcj_encoder* enc = 0;
+  mdcjo_encoder* oenc = 0;
   mdcp_encoder* penc = 0;
   mdcl_encoder* lenc = 0;
   if (lz77 && mdcl_create(reader->getDevice(), w, h, MDCL_GRAY8, MDCL_FILTER_ADAPTIVE, chain, chunk, &lenc) != MDCL_OK) {
@@ -219,8 +235,12 @@ int main(int argc, char** argv) {
     fprintf(stderr, "rectifyDataset: %s\n", mdcp_last_error());
     return 1;
   }
-  if (!png && mdcj_create(reader->getDevice(), w, h, quality, chunk, &enc) != MDCJ_OK) {
+  if (!png && !optimal && mdcj_create(reader->getDevice(), w, h, quality, chunk, &enc) != MDCJ_OK) {
     fprintf(stderr, "rectifyDataset: %s\n", mdcj_last_error());
+    return 1;
+  }
+  if (optimal && mdcjo_create(reader->getDevice(), w, h, quality, chunk, &oenc) != MDCJO_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", mdcjo_last_error());
     return 1;
   }
   float* d_frames = 0;
@@ -232,8 +252,9 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (lz77 ? mdcl_output_device(lenc, &d_out, &slot, &d_sizes) != MDCL_OK
-           : png ? mdcp_output_device(penc, &d_out, &slot, &d_sizes) != MDCP_OK : mdcj_output_device(enc, &d_out, &slot, &d_sizes) != MDCJ_OK) {
-    fprintf(stderr, "rectifyDataset: %s\n", lz77 ? mdcl_last_error() : png ? mdcp_last_error() : mdcj_last_error());
+           : png ? mdcp_output_device(penc, &d_out, &slot, &d_sizes) != MDCP_OK
+           : optimal ? mdcjo_output_device(oenc, &d_out, &slot, &d_sizes) != MDCJO_OK : mdcj_output_device(enc, &d_out, &slot, &d_sizes) != MDCJ_OK) {
+    fprintf(stderr, "rectifyDataset: %s\n", lz77 ? mdcl_last_error() : png ? mdcp_last_error() : optimal ? mdcjo_last_error() : mdcj_last_error());
     return 1;
   }
   mdcz_writer* zip = 0;
@@ -258,8 +279,9 @@ int main(int argc, char** argv) {
     // positions without a frame are encoded too (whatever they hold is a legal input) and left out of the archive
     if (lz77 ? mdcl_encode_f32_device(lenc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCL_OK
         : png ? mdcp_encode_f32_device(penc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCP_OK
-              : mdcj_encode_f32_device(enc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJ_OK) {
-      fprintf(stderr, "rectifyDataset: %s\n", lz77 ? mdcl_last_error() : png ? mdcp_last_error() : mdcj_last_error());
+        : optimal ? mdcjo_encode_f32_device(oenc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJO_OK
+                  : mdcj_encode_f32_device(enc, d_frames, (int64_t)frame, n, d_out, slot, d_sizes, 0) != MDCJ_OK) {
+      fprintf(stderr, "rectifyDataset: %s\n", lz77 ? mdcl_last_error() : png ? mdcp_last_error() : optimal ? mdcjo_last_error() : mdcj_last_error());
       status = 1;
       break;
     }
@@ -275,6 +297,7 @@ int main(int argc, char** argv) {
   }
   mdc_device_free(ctx, d_frames);
   mdcj_destroy(enc);
+  mdcjo_destroy(oenc);
   mdcp_destroy(penc);
   mdcl_destroy(lenc);
   if (status) {
