@@ -85,7 +85,7 @@ MDC_API void mdch_reader_raw_dims(mdch_reader*, int wh[2]); /* getRawSize() */
 MDC_API void mdch_reader_set_threads(mdch_reader*, int n);       /* setDecodeThreads() */
 MDC_API void mdch_reader_set_prefetch(mdch_reader*, int frames); /* setPrefetch() */
 MDC_API void mdch_reader_set_lookahead(mdch_reader*, int frames); /* setResultLookahead(): getImage results made ahead on JPEG sequences read in order */
-MDC_API void mdch_reader_set_gpu_png(mdch_reader*, int mode);     /* setGpuPngMode(): 0 host, 1 the stream classes that win on the device, 2 every eligible stream */
+MDC_API void mdch_reader_set_gpu_png(mdch_reader*, int mode);     /* setGpuPngMode(): 0 host, 1 the stream classes that win on the device, 2 every eligible stream, 3 the same through libmdc_pngdx.so */
 MDC_API long mdch_reader_png_device_frames(mdch_reader*);         /* frames libmdc_pngd.so decoded for getImagesDevice over the reader's life */
 MDC_API void mdch_reader_set_gpu_jpeg(mdch_reader*, int stage);   /* setGpuJpegStage(): 0 host, 1 device inverse DCT, 2 (or any other) device Huffman too */
 MDC_API const char* mdch_reader_last_error(mdch_reader*);

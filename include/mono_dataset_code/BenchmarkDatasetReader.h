@@ -108,9 +108,10 @@ class MDC_API DatasetReader {
   // getImagesDevice on PNG sequences (8-bit grayscale, non-interlaced): the decode threads only walk the chunks, libmdc_pngd.so (loaded
   // at first use from the directory of this library, or MDC_LIB_PNGD) inflates, checks and unfilters on the GPU and the fused pass reads
   // the pixels where they are.  Mode 1 (default): the stream classes measured faster than the host decoder (a single
-  // final Huffman-only block, what bin/rectifyDataset frames=png writes); 2: every eligible stream;
+  // final Huffman-only block, what bin/rectifyDataset frames=png writes); 2: every eligible stream; 3: every eligible stream through
+  // libmdc_pngdx.so (include/mdc_pngdx.h; MDC_LIB_PNGDX), whose inflate is parallel for streams with matches too;
   // 0: the host decoder.  A stream the device refuses goes to the host decoder.  Same bytes in every mode.  setGpuPng(on) = 1 / 0;
-  // MDC_GPU_PNG=0|1|2 in the environment.  getImages, getImage and getImagesRawDevice decode PNG on the host.
+  // MDC_GPU_PNG=0|1|2|3 in the environment.  getImages, getImage and getImagesRawDevice decode PNG on the host.
   void setGpuPng(bool on);
   void setGpuPngMode(int mode);
   long pngDeviceFrames() const;  // frames the device decoder produced so far

@@ -364,13 +364,14 @@ LIB_PNGD = os.path.join(PKG, "libmdc_pngd.so")
 PNGD_SOURCE = os.path.join(CSRC, "mdc_pngd.hip")
 PNGD_CORE = os.path.join(CSRC, "png_inflate_core.h")
 PNGD_EXPORT_MAP = os.path.join(CSRC, "mdc_pngd_exports.map")
+PNG_DECODE_KERNELS = os.path.join(CSRC, "png_decode_kernels.h")  # what the two PNG decoder libraries share: the four kernels, host helpers
 
 
 def build_pngd(force=False):
-    """libmdc_pngd.so: the device PNG decoder (include/mdc_pngd.h) -- one translation unit plus the core header it shares with the CPU
-    test program, independent of every other library here and outside libmdc_hip.so's build identity.  The dataset reader loads it
-    at run time (csrc/host/device_lanes.cpp), nothing links it."""
-    if force or _stale(LIB_PNGD, [PNGD_SOURCE, PNGD_CORE, os.path.join(INC, "mdc_pngd.h"), PNGD_EXPORT_MAP]):
+    """libmdc_pngd.so: the device PNG decoder (include/mdc_pngd.h) -- one translation unit, the core header it shares with the CPU
+    test program and the kernels' header it shares with mdc_pngdx.hip, independent of every other library here and outside
+    libmdc_hip.so's build identity.  The dataset reader loads it at run time (csrc/host/device_lanes.cpp), nothing links it."""
+    if force or _stale(LIB_PNGD, [PNGD_SOURCE, PNGD_CORE, PNG_DECODE_KERNELS, os.path.join(INC, "mdc_pngd.h"), PNGD_EXPORT_MAP]):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
               "-Wall", "-I" + INC, PNGD_SOURCE, "-Wl,--version-script=" + PNGD_EXPORT_MAP, "-o", LIB_PNGD])
     return LIB_PNGD
@@ -381,6 +382,31 @@ def build_pngd_core_program(out, sanitize=True):
     UndefinedBehaviorSanitizer (tests/test_pngd_cpu.py).  Pure host code: no HIP, no library of ours."""
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
     _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pngd_core.cpp"), "-o", out])
+    return out
+
+
+LIB_PNGDX = os.path.join(PKG, "libmdc_pngdx.so")
+PNGDX_SOURCE = os.path.join(CSRC, "mdc_pngdx.hip")
+PNGDX_CORE = os.path.join(CSRC, "png_tokens_core.h")  # the token path, phase by phase: libmdc_pngdx.so and a CPU test program
+PNGDX_EXPORT_MAP = os.path.join(CSRC, "mdc_pngdx_exports.map")
+
+
+def build_pngdx(force=False):
+    """libmdc_pngdx.so: the device PNG decoder with a parallel inflate for streams with matches (include/mdc_pngdx.h) -- one
+    translation unit, the kernels' header it shares with mdc_pngd.hip and the two core headers it shares with the CPU test programs;
+    it links neither libmdc_pngd.so nor libmdc_hip.so and is outside the product's build identity.  The dataset reader loads it at
+    run time when MDC_GPU_PNG=3 asks for it."""
+    if force or _stale(LIB_PNGDX, [PNGDX_SOURCE, PNGD_CORE, PNGDX_CORE, PNG_DECODE_KERNELS, os.path.join(INC, "mdc_pngdx.h"), PNGDX_EXPORT_MAP]):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+              "-Wall", "-I" + INC, PNGDX_SOURCE, "-Wl,--version-script=" + PNGDX_EXPORT_MAP, "-o", LIB_PNGDX])
+    return LIB_PNGDX
+
+
+def build_pngdx_core_program(out, sanitize=True):
+    """tests/native/pngdx_core.cpp: png_tokens_core.h (the token path of libmdc_pngdx.so) as a stand-alone program (its own main),
+    under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_pngdx_cpu.py).  Pure host code: no HIP, no library of ours."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pngdx_core.cpp"), "-o", out])
     return out
 
 
@@ -460,6 +486,7 @@ def build_all(force=False):
     build_pngw_rgb(force)
     build_pnglz(force)
     build_pngd(force)
+    build_pngdx(force)
     build_debug()
     build_fault_injection()
     return LIB_HIP, LIB_HOST, LIB_MULTI

@@ -360,6 +360,18 @@ PNGD_API = {  # include/mdc_pngd.h (libmdc_pngd.so: the device PNG decoder, a li
     "mdci_stream": (_vp, [_vp]),
     "mdci_synchronize": (_i, [_vp]),
 }
+PNGDX_API = {  # include/mdc_pngdx.h (libmdc_pngdx.so: the device PNG decoder with the parallel inflate, a library of its own)
+    "mdcx_last_error": (_cp, []),
+    "mdcx_scratch_bytes": (_i64, [_i, _i, _i]),
+    "mdcx_create": (_i, [_i, _i, _i, _i, _P(_vp)]),
+    "mdcx_destroy": (None, [_vp]),
+    "mdcx_decode_device": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "mdcx_decode_host": (_i, [_vp, _vp, _vp, _i, _vp, _P(_vp)]),
+    "mdcx_profile": (_i, [_vp, _i]),
+    "mdcx_kernel_ms": (_i, [_vp, _P(_f)]),
+    "mdcx_stream": (_vp, [_vp]),
+    "mdcx_synchronize": (_i, [_vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
@@ -370,6 +382,7 @@ LIB_PNGW_PATH = os.path.join(_PKG, "libmdc_pngw.so")
 LIB_PNGW_RGB_PATH = os.path.join(_PKG, "libmdc_pngw_rgb.so")
 LIB_PNGLZ_PATH = os.path.join(_PKG, "libmdc_pnglz.so")
 LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
+LIB_PNGDX_PATH = os.path.join(_PKG, "libmdc_pngdx.so")
 _hip = None
 _host = None
 _bench = None
@@ -380,6 +393,7 @@ _pngw = None
 _pngw_rgb = None
 _pnglz = None
 _pngd = None
+_pngdx = None
 
 
 def _share_hip_runtime_with_torch():
@@ -487,6 +501,15 @@ def pngd_lib():
         _share_hip_runtime_with_torch()
         _pngd = _load(LIB_PNGD_PATH, PNGD_API)
     return _pngd
+
+
+def pngdx_lib():
+    """libmdc_pngdx.so: the PNG decoder with a parallel inflate for streams with matches (include/mdc_pngdx.h)."""
+    global _pngdx
+    if _pngdx is None:
+        _share_hip_runtime_with_torch()
+        _pngdx = _load(LIB_PNGDX_PATH, PNGDX_API)
+    return _pngdx
 
 
 def hip_lib():
@@ -1365,40 +1388,49 @@ class PngEncoder:
 
 
 PNGD_PATHS = {1: "parallel", 2: "stored", 3: "general"}  # MDCI_PATH_*
+PNGDX_PATHS = {1: "parallel", 2: "stored", 3: "general", 4: "tokens"}  # MDCX_PATH_*
 
 
 class PngDecoder:
     """One mdci_decoder (include/mdc_pngd.h): the zlib streams of w x h 8-bit grayscale PNG frames -> pixels on the device.  A
-    status is reason | path << 16 (reason 0: decoded); status_fields() splits an array of them."""
+    status is reason | path << 16 (reason 0: decoded); status_fields() splits an array of them.  matches="parallel": one
+    mdcx_decoder (include/mdc_pngdx.h) instead, the same interface with a parallel inflate for streams with matches."""
 
-    def __init__(self, w, h, max_images=1, device=-1):
-        self._L = pngd_lib()
+    def __init__(self, w, h, max_images=1, device=-1, matches="wave"):
+        if matches not in ("wave", "parallel"):
+            raise ValueError("matches is 'wave' (libmdc_pngd.so) or 'parallel' (libmdc_pngdx.so), not %r" % (matches,))
+        self.matches = matches
+        self._L, self._prefix = (pngdx_lib(), "mdcx_") if matches == "parallel" else (pngd_lib(), "mdci_")
         self.w, self.h, self.max_images = int(w), int(h), int(max_images)
         h_ = _vp()
-        self._check(self._L.mdci_create(int(device), self.w, self.h, self.max_images, C.byref(h_)))
+        self._check(self._fn("create")(int(device), self.w, self.h, self.max_images, C.byref(h_)))
         self._h = h_
-        self.scratch_bytes = int(self._L.mdci_scratch_bytes(self.w, self.h, self.max_images))
+        self.scratch_bytes = int(self._fn("scratch_bytes")(self.w, self.h, self.max_images))
+
+    def _fn(self, name):
+        return getattr(self._L, self._prefix + name)
 
     def _check(self, rc):
         if rc < 0:
-            raise MdcError(int(rc), self._L.mdci_last_error().decode())
+            raise MdcError(int(rc), self._fn("last_error")().decode())
         return rc
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.mdci_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     __del__ = close
 
     def profile(self, on=True):
-        """HIP events around the four kernels of every decode_device call from now on (kernel_ms reads the last call's)"""
-        self._check(self._L.mdci_profile(self._h, int(bool(on))))
+        """HIP events around the kernels of every decode_device call from now on (kernel_ms reads the last call's)"""
+        self._check(self._fn("profile")(self._h, int(bool(on))))
 
     def kernel_ms(self):
-        """-> (front, wave-per-image inflate, checks, unfilter) of the last timed call, in ms; waits for it"""
-        ms = (_f * 4)()
-        self._check(self._L.mdci_kernel_ms(self._h, ms))
+        """-> (front, wave-per-image inflate, checks, unfilter) of the last timed call, in ms; waits for it.  matches="parallel":
+        (front, tokens, wave-per-image inflate, checks, unfilter)"""
+        ms = (_f * (5 if self.matches == "parallel" else 4))()
+        self._check(self._fn("kernel_ms")(self._h, ms))
         return tuple(float(v) for v in ms)
 
     @staticmethod
@@ -1410,7 +1442,7 @@ class PngDecoder:
     def decode_device(self, d_slots, slot_bytes, d_sizes, n, d_frames, d_status, skip_head=0, skip_tail=0, frame_stride=None, stream=0):
         """device addresses throughout: n slots of slot_bytes, int32 sizes -> frames frame_stride bytes apart (default w * h) and
         int32 statuses; enqueues on `stream` and does not synchronise"""
-        self._check(self._L.mdci_decode_device(self._h, d_slots, int(slot_bytes), d_sizes, int(skip_head), int(skip_tail), int(n), d_frames,
+        self._check(self._fn("decode_device")(self._h, d_slots, int(slot_bytes), d_sizes, int(skip_head), int(skip_tail), int(n), d_frames,
                                                self.w * self.h if frame_stride is None else int(frame_stride), d_status, _stream(stream)))
 
     def decode_host(self, streams):
@@ -1422,7 +1454,7 @@ class PngDecoder:
         sizes = np.asarray([k.size for k in keep], np.int64)
         status = np.zeros(max(n, 1), np.int32)
         d_frames = _vp()
-        self._check(self._L.mdci_decode_host(self._h, ptrs, _np_ptr(sizes) if n else None, n, _np_ptr(status), C.byref(d_frames)))
+        self._check(self._fn("decode_host")(self._h, ptrs, _np_ptr(sizes) if n else None, n, _np_ptr(status), C.byref(d_frames)))
         return status[:n], d_frames.value
 
 
@@ -1639,7 +1671,7 @@ class DatasetReader:
 
     def set_gpu_png(self, mode):
         """getImagesDevice on PNG frames.  True / 1: the stream classes that win go to the device decoder; 2: every eligible stream;
-        False / 0: the host decoder."""
+        3: every eligible stream through libmdc_pngdx.so (parallel inflate for streams with matches); False / 0: the host decoder."""
         self._L.mdch_reader_set_gpu_png(self._h, int(mode))
 
     def png_device_frames(self):

@@ -129,11 +129,12 @@ struct LaneRun {
 
   // The lane's PNG decoder, for n frames of the reader's size (0: none to be had -- the frames take the host decoder)
   void* png_decoder(int n) {
-    if (lane.pngd && lane.pngd_frames >= n) return lane.pngd;
-    if (lane.pngd) c.png->destroy(lane.pngd);
+    if (lane.pngd && lane.pngd_from == c.png && lane.pngd_frames >= n) return lane.pngd;
+    if (lane.pngd && lane.pngd_from) lane.pngd_from->destroy(lane.pngd);  // too small, or the other library's (the mode changed)
     lane.pngd = 0;
     const int want = std::max(n, c.C);
     if (c.png->create(lane.device, c.env.W, c.env.H, want, &lane.pngd) != 0) lane.pngd = 0;
+    lane.pngd_from = lane.pngd ? c.png : 0;
     lane.pngd_frames = lane.pngd ? want : 0;
     return lane.pngd;
   }
@@ -347,7 +348,7 @@ int run_batch(const BatchEnv& env, const std::vector<Lane*>& use, int first, int
   const int slots = (env.gpu_jpeg >= 2 && per_lane > 1) ? 2 * C : (env.gpu_jpeg >= 2 ? C : kRingFrames), RG = slots / C;
   const int active = std::min(L, nchunks);
   const int rec_pitch = ((env.W + 7) / 8 + 11) / 12 * 12, rec_rows = ((env.H + 7) / 8 + 11) / 12 * 12;
-  Call c = {env, first, count, C, RG, active, rectify, flags, out, dev, valid, rec_pitch, rec_rows, 128 + (size_t)rec_pitch * rec_rows * 128, {}, {}, (dev && env.gpu_png) ? pngd_api() : 0};
+  Call c = {env, first, count, C, RG, active, rectify, flags, out, dev, valid, rec_pitch, rec_rows, 128 + (size_t)rec_pitch * rec_rows * 128, {}, {}, (dev && env.gpu_png) ? pngd_api(env.gpu_png >= 3) : 0};
   // a ring buffer holds a decoded frame, or (stage 1) a coefficient record -- 2 bytes per pixel --, or (stage 2) a stream: the
   // compressed bytes + 5 KB; a file stage 2 does not take, or whose stream does not fit, is decoded to pixels on the host
   const size_t want_bytes = env.gpu_jpeg == 1 ? std::max(env.frame_bytes, c.rec_bytes) : env.frame_bytes;

@@ -42,7 +42,8 @@ struct BatchEnv {
   bool quiet;  // the batch behind getImage's lookahead: a frame that fails is reported when the caller asks for it
   // GPU JPEG stage: JPEG frames travel as coefficient records (2 bytes per pixel + table), the inverse DCT runs on the device
   int gpu_jpeg;  // 0: JPEG decoded on the host; 1: host Huffman + device inverse DCT; 2: device Huffman + inverse DCT
-  // device PNG decoder, getImagesDevice only: 0 PNG decoded on the host, 1 the stream classes of kPngDefaultClasses, 2 every eligible one
+  // device PNG decoder, getImagesDevice only: 0 PNG decoded on the host, 1 the stream classes of kPngDefaultClasses, 2 every eligible one,
+  // 3 every eligible one by libmdc_pngdx.so (parallel inflate for streams with matches)
   int gpu_png;
 };
 

@@ -90,7 +90,7 @@ struct DatasetReader::State {
 
 DatasetReader::DatasetReader(std::string folder) : s_(new State()) {
   if (const char* e = std::getenv("MDC_GPU_JPEG")) s_->gpu_jpeg = std::max(0, std::min(2, std::atoi(e)));
-  if (const char* e = std::getenv("MDC_GPU_PNG")) s_->gpu_png = std::max(0, std::min(2, std::atoi(e)));
+  if (const char* e = std::getenv("MDC_GPU_PNG")) s_->gpu_png = std::max(0, std::min(3, std::atoi(e)));
   if (const char* e = std::getenv("MDC_READER_LOOKAHEAD")) s_->lookahead = std::max(0, std::min((int)kRingFrames, std::atoi(e)));
   State& s = *s_;
   s.path = folder;
@@ -210,7 +210,7 @@ void DatasetReader::setResultLookahead(int frames) {
   if (!s_->lookahead) s_->drop_ahead();
 }
 void DatasetReader::setGpuPng(bool on) { s_->gpu_png = on ? 1 : 0; }
-void DatasetReader::setGpuPngMode(int mode) { s_->gpu_png = std::max(0, std::min(2, mode)); }
+void DatasetReader::setGpuPngMode(int mode) { s_->gpu_png = std::max(0, std::min(3, mode)); }
 long DatasetReader::pngDeviceFrames() const {
   long n = 0;
   for (const mdc_host::Lane& ln : s_->dev.lanes) n += ln.png_frames;

@@ -38,31 +38,38 @@ bool DeviceLanes::load_multi() {
   return true;
 }
 
-const PngdApi* pngd_api() {
-  static const PngdApi* api = []() -> const PngdApi* {
-    std::string path;
-    if (const char* e = std::getenv("MDC_LIB_PNGD")) {
-      path = e;
-    } else {
-      Dl_info info;
-      if (dladdr((void*)&open_device_context, &info) && info.dli_fname) {
-        path = info.dli_fname;
-        const size_t sl = path.rfind('/');
-        path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
-      }
-      path += "libmdc_pngd.so";
+static const PngdApi* load_pngd(const char* env, const char* file, const char* prefix) {
+  std::string path;
+  if (const char* e = std::getenv(env)) {
+    path = e;
+  } else {
+    Dl_info info;
+    if (dladdr((void*)&open_device_context, &info) && info.dli_fname) {
+      path = info.dli_fname;
+      const size_t sl = path.rfind('/');
+      path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
     }
-    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);  // holds a HIP module: never unmapped again
-    if (!lib) return 0;
-    static PngdApi a;
-    a.create = (int (*)(int, int, int, int, void**))dlsym(lib, "mdci_create");
-    a.destroy = (void (*)(void*))dlsym(lib, "mdci_destroy");
-    a.decode_host = (int (*)(void*, const void* const*, const long long*, int, int*, const unsigned char**))dlsym(lib, "mdci_decode_host");
-    a.last_error = (const char* (*)())dlsym(lib, "mdci_last_error");
-    a.stream = (void* (*)(void*))dlsym(lib, "mdci_stream");
-    a.synchronize = (int (*)(void*))dlsym(lib, "mdci_synchronize");
-    return a.create && a.destroy && a.decode_host && a.last_error && a.stream && a.synchronize ? &a : 0;
-  }();
+    path += file;
+  }
+  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);  // holds a HIP module: never unmapped again
+  if (!lib) return 0;
+  const std::string pre(prefix);
+  PngdApi* a = new PngdApi;  // one per library and process, never freed
+  a->create = (int (*)(int, int, int, int, void**))dlsym(lib, (pre + "create").c_str());
+  a->destroy = (void (*)(void*))dlsym(lib, (pre + "destroy").c_str());
+  a->decode_host = (int (*)(void*, const void* const*, const long long*, int, int*, const unsigned char**))dlsym(lib, (pre + "decode_host").c_str());
+  a->last_error = (const char* (*)())dlsym(lib, (pre + "last_error").c_str());
+  a->stream = (void* (*)(void*))dlsym(lib, (pre + "stream").c_str());
+  a->synchronize = (int (*)(void*))dlsym(lib, (pre + "synchronize").c_str());
+  return a->create && a->destroy && a->decode_host && a->last_error && a->stream && a->synchronize ? a : 0;
+}
+
+const PngdApi* pngd_api(bool parallel_matches) {
+  if (parallel_matches) {
+    static const PngdApi* apix = load_pngd("MDC_LIB_PNGDX", "libmdc_pngdx.so", "mdcx_");
+    return apix;
+  }
+  static const PngdApi* api = load_pngd("MDC_LIB_PNGD", "libmdc_pngd.so", "mdci_");
   return api;
 }
 
@@ -205,7 +212,7 @@ std::vector<Lane*> DeviceLanes::for_batch(bool device_outputs) {
 void DeviceLanes::close() {
   for (Lane& ln : lanes) {
     ln.ring_block.release();
-    if (ln.pngd) pngd_api()->destroy(ln.pngd);
+    if (ln.pngd && ln.pngd_from) ln.pngd_from->destroy(ln.pngd);
     ln.pngd = 0;
     if ((!multi_ || ln.twin) && ln.gpu) mdc_destroy(ln.gpu);
   }

@@ -27,11 +27,13 @@ struct PngdApi {
   int (*synchronize)(void*) = 0;
 };
 // The library next to this one (or the file MDC_LIB_PNGD names), opened once per process and never closed; 0 when it is not there:
-// PNG frames then take the host decoder, silently.
-const PngdApi* pngd_api();
+// PNG frames then take the host decoder, silently.  parallel_matches: libmdc_pngdx.so (include/mdc_pngdx.h; MDC_LIB_PNGDX), the same
+// interface under mdcx_ names, by the same rules.
+const PngdApi* pngd_api(bool parallel_matches = false);
 
 struct Lane {
-  void* pngd = 0;  // the lane's mdci_decoder, made at first use for pngd_frames frames of the reader's size
+  void* pngd = 0;  // the lane's mdci_decoder (or mdcx_decoder), made at first use for pngd_frames frames of the reader's size
+  const PngdApi* pngd_from = 0;  // the library that made it
   int pngd_frames = 0;
   long png_frames = 0;  // statistics: frames it decoded
   mdc_ctx* gpu = 0;

@@ -13,7 +13,8 @@
 // encoder converts them (rintf, clamped to 0..255, NaN -> 0) and encoded on the device by include/mdc_pngw.h; no JPEG encoder is made.
 // compress=lz77 (with frames=png only; chain=N, 1..64, default 4, is its match depth) encodes the frames, and vignette.png, by
 // include/mdc_pnglz.h instead: the same pixels in files that are never larger.  Such files carry distance codes, which the reader
-// decodes on the host unless MDC_GPU_PNG=2 sends them to the device decoder's general path.  The default, compress=huffman, writes
+// decodes on the host unless MDC_GPU_PNG=2 sends them to the device decoder's general path or MDC_GPU_PNG=3 to the parallel inflate of
+// include/mdc_pngdx.h.  The default, compress=huffman, writes
 // today's files byte for byte.  A bad value is refused with one line before anything is opened or created.
 // huffman=optimal (with frames=jpg only) encodes the frames by include/mdc_jopt.h instead: one Huffman table pair per frame, the file
 // libjpeg writes with optimize_coding (PIL: optimize=True) -- the same pixels in smaller files.  The default, huffman=standard, is the
