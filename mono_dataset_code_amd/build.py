@@ -1,9 +1,14 @@
 """Build recipe for the native libraries (in-tree, no install step).
 
-  libmdc_hip.so   hipcc, gfx950 only   HIP kernels + the C ABI (include/mdc_hip.h)
-  libmdc_host.so  g++                  drop-in C++ classes + C facade (include/mdc_host.h)
+  libmdc_hip.so    hipcc, gfx950 only   HIP kernels + the C ABI (include/mdc_hip.h); its sources are its build identity (code_id)
+  libmdc_host.so   g++                  drop-in C++ classes + C facade (include/mdc_host.h)
+  libmdc_multi.so, libmdc_bench.so      one process on N GPUs; measurement and test utilities
+  the codec libraries, hipcc, gfx950    libmdc_jenc.so, libmdc_jopt.so, libmdc_zipw.so, libmdc_pngw.so, libmdc_pngw_rgb.so,
+                                        libmdc_pnglz.so, libmdc_pngd.so, libmdc_pngdx.so: one translation unit each over shared core
+                                        headers, all by one rule (_build_codec), outside libmdc_hip.so's build identity
+  bin/                                  the programs; tests/native/ programs are built into a place the tests name
 
-Both land next to this file so they travel with the source tree to the GPU box.
+All land next to this file so they travel with the source tree to the GPU box.
 `python -m mono_dataset_code_amd.build` rebuilds whatever is out of date.
 """
 import os
@@ -249,19 +254,39 @@ def build_bench(force=False):
     return LIB_BENCH
 
 
+CODEC_HOST = os.path.join(CSRC, "codec_host.h")  # what every codec library's host side has: the last error, the device guard, device resolution
+
+
+def _build_codec(out, source, deps, export_map, zipw=False, defines=(), force=False):
+    """One codec library: a single translation unit (`source` and the headers in `deps`), a library of its own outside
+    libmdc_hip.so's build identity.  zipw: it stands on libmdc_zipw.so, which is built first and linked."""
+    if zipw:
+        build_zipw(force)
+    if force or _stale(out, [source, CODEC_HOST] + deps + [export_map] + ([LIB_ZIPW] if zipw else [])):
+        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall"] +
+             ["-D" + d for d in defines] + ["-I" + INC, source] + (["-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN"] if zipw else []) +
+             ["-Wl,--version-script=" + export_map, "-o", out])
+    return out
+
+
+def _build_native_program(source, out, sanitize=True):
+    """A stand-alone test program of tests/native/ (its own main, pure host code over a header of csrc/), under AddressSanitizer and
+    UndefinedBehaviorSanitizer."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", source), "-o", out])
+    return out
+
+
 LIB_JENC = os.path.join(PKG, "libmdc_jenc.so")
 JENC_SOURCE = os.path.join(CSRC, "mdc_jenc.hip")
 JENC_EXPORT_MAP = os.path.join(CSRC, "mdc_jenc_exports.map")
-JPEG_ENCODE_CORE = os.path.join(CSRC, "jpeg_encode_core.h")  # what the two JPEG encoder libraries share: tables, DCT, block walker, scan, host helpers
+JPEG_ENCODE_CORE = os.path.join(CSRC, "jpeg_encode_core.h")  # what the two JPEG encoder libraries share: tables, DCT, block walker, scan, host side
 
 
 def build_jenc(force=False):
     """libmdc_jenc.so: the device baseline JPEG encoder (include/mdc_jenc.h) -- one translation unit, independent of libmdc_hip.so
     and outside its build identity."""
-    if force or _stale(LIB_JENC, [JENC_SOURCE, JPEG_ENCODE_CORE, os.path.join(INC, "mdc_jenc.h"), JENC_EXPORT_MAP]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, JENC_SOURCE, "-Wl,--version-script=" + JENC_EXPORT_MAP, "-o", LIB_JENC])
-    return LIB_JENC
+    return _build_codec(LIB_JENC, JENC_SOURCE, [JPEG_ENCODE_CORE, os.path.join(INC, "mdc_jenc.h")], JENC_EXPORT_MAP, force=force)
 
 
 LIB_JOPT = os.path.join(PKG, "libmdc_jopt.so")
@@ -274,18 +299,13 @@ def build_jopt(force=False):
     """libmdc_jopt.so: the device JPEG encoder with per-frame optimal Huffman tables (include/mdc_jopt.h) -- one translation unit,
     the header it shares with mdc_jenc.hip and the table rule's header; it links neither libmdc_jenc.so nor libmdc_hip.so and is
     outside the product's build identity."""
-    if force or _stale(LIB_JOPT, [JOPT_SOURCE, JPEG_ENCODE_CORE, JOPT_TABLE, os.path.join(INC, "mdc_jopt.h"), JOPT_EXPORT_MAP]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, JOPT_SOURCE, "-Wl,--version-script=" + JOPT_EXPORT_MAP, "-o", LIB_JOPT])
-    return LIB_JOPT
+    return _build_codec(LIB_JOPT, JOPT_SOURCE, [JPEG_ENCODE_CORE, JOPT_TABLE, os.path.join(INC, "mdc_jopt.h")], JOPT_EXPORT_MAP, force=force)
 
 
 def build_jopt_table_program(out, sanitize=True):
     """tests/native/jopt_table.cpp: csrc/jpeg_optimal_table.h (the table rule of libmdc_jopt.so) as a stand-alone program, under
     AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_jopt_cpu.py).  Pure host code."""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
-    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "jopt_table.cpp"), "-o", out])
-    return out
+    return _build_native_program("jopt_table.cpp", out, sanitize)
 
 
 LIB_ZIPW = os.path.join(PKG, "libmdc_zipw.so")
@@ -296,10 +316,7 @@ ZIPW_EXPORT_MAP = os.path.join(CSRC, "mdc_zipw_exports.map")
 def build_zipw(force=False):
     """libmdc_zipw.so: ZIP archives of device-resident files, checksummed and laid out on the device (include/mdc_zipw.h) -- one
     translation unit, independent of every other library here and outside libmdc_hip.so's build identity."""
-    if force or _stale(LIB_ZIPW, [ZIPW_SOURCE, os.path.join(INC, "mdc_zipw.h"), ZIPW_EXPORT_MAP]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, ZIPW_SOURCE, "-Wl,--version-script=" + ZIPW_EXPORT_MAP, "-o", LIB_ZIPW])
-    return LIB_ZIPW
+    return _build_codec(LIB_ZIPW, ZIPW_SOURCE, [os.path.join(INC, "mdc_zipw.h")], ZIPW_EXPORT_MAP, force=force)
 
 
 LIB_PNGW = os.path.join(PKG, "libmdc_pngw.so")
@@ -312,11 +329,8 @@ PNG_ENCODE_CORE = os.path.join(CSRC, "png_encode_core.h")  # what else the three
 def build_pngw(force=False):
     """libmdc_pngw.so: the device PNG encoder (include/mdc_pngw.h) -- one translation unit and the two headers it shares with
     mdc_pnglz.hip, on top of libmdc_zipw.so (for the IDAT chunk's CRC-32), independent of libmdc_hip.so and outside its build identity."""
-    build_zipw(force)
-    if force or _stale(LIB_PNGW, [PNGW_SOURCE, PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_zipw.h"), PNGW_EXPORT_MAP, LIB_ZIPW]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGW_EXPORT_MAP, "-o", LIB_PNGW])
-    return LIB_PNGW
+    return _build_codec(LIB_PNGW, PNGW_SOURCE, [PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_zipw.h")], PNGW_EXPORT_MAP,
+                        zipw=True, force=force)
 
 
 LIB_PNGW_RGB = os.path.join(PKG, "libmdc_pngw_rgb.so")
@@ -326,13 +340,8 @@ PNGW_RGB_EXPORT_MAP = os.path.join(CSRC, "mdc_pngw_rgb_exports.map")
 def build_pngw_rgb(force=False):
     """libmdc_pngw_rgb.so: the device PNG encoder for 8-bit RGB images (include/mdc_pngw_rgb.h) -- mdc_pngw.hip built with
     -DMDCP_RGB8_LIBRARY, a library of its own beside libmdc_pngw.so (which stays what it is), on top of libmdc_zipw.so."""
-    build_zipw(force)
-    if force or _stale(LIB_PNGW_RGB, [PNGW_SOURCE, PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pngw_rgb.h"), os.path.join(INC, "mdc_zipw.h"),
-                                      PNGW_RGB_EXPORT_MAP, LIB_ZIPW]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-DMDCP_RGB8_LIBRARY=1", "-I" + INC, PNGW_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN",
-              "-Wl,--version-script=" + PNGW_RGB_EXPORT_MAP, "-o", LIB_PNGW_RGB])
-    return LIB_PNGW_RGB
+    return _build_codec(LIB_PNGW_RGB, PNGW_SOURCE, [PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pngw.h"), os.path.join(INC, "mdc_pngw_rgb.h"),
+                                                    os.path.join(INC, "mdc_zipw.h")], PNGW_RGB_EXPORT_MAP, zipw=True, defines=["MDCP_RGB8_LIBRARY=1"], force=force)
 
 
 LIB_PNGLZ = os.path.join(PKG, "libmdc_pnglz.so")
@@ -345,44 +354,34 @@ def build_pnglz(force=False):
     """libmdc_pnglz.so: the device PNG encoder with LZ77 matches (include/mdc_pnglz.h), gray and RGB in one library -- one
     translation unit and the two headers it shares with mdc_pngw.hip, on top of libmdc_zipw.so; it links neither libmdc_pngw.so nor
     libmdc_pngw_rgb.so, and it is outside libmdc_hip.so's build identity."""
-    build_zipw(force)
-    if force or _stale(LIB_PNGLZ, [PNGLZ_SOURCE, PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mdc_zipw.h"), PNGLZ_EXPORT_MAP, LIB_ZIPW]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, PNGLZ_SOURCE, "-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN", "-Wl,--version-script=" + PNGLZ_EXPORT_MAP, "-o", LIB_PNGLZ])
-    return LIB_PNGLZ
+    return _build_codec(LIB_PNGLZ, PNGLZ_SOURCE, [PNG_BLOCK, PNG_ENCODE_CORE, os.path.join(INC, "mdc_pnglz.h"), os.path.join(INC, "mdc_zipw.h")], PNGLZ_EXPORT_MAP,
+                        zipw=True, force=force)
 
 
 def build_pnglz_block_program(out, sanitize=True):
     """tests/native/pnglz_block.cpp: csrc/png_block.h (the code builder and header writer of the PNG encoder libraries) as a
     stand-alone program, under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_pnglz_cpu.py).  Pure host code."""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
-    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pnglz_block.cpp"), "-o", out])
-    return out
+    return _build_native_program("pnglz_block.cpp", out, sanitize)
 
 
 LIB_PNGD = os.path.join(PKG, "libmdc_pngd.so")
 PNGD_SOURCE = os.path.join(CSRC, "mdc_pngd.hip")
 PNGD_CORE = os.path.join(CSRC, "png_inflate_core.h")
 PNGD_EXPORT_MAP = os.path.join(CSRC, "mdc_pngd_exports.map")
-PNG_DECODE_KERNELS = os.path.join(CSRC, "png_decode_kernels.h")  # what the two PNG decoder libraries share: the four kernels, host helpers
+PNG_DECODE_KERNELS = os.path.join(CSRC, "png_decode_kernels.h")  # what the two PNG decoder libraries share: the four kernels, the host side
 
 
 def build_pngd(force=False):
     """libmdc_pngd.so: the device PNG decoder (include/mdc_pngd.h) -- one translation unit, the core header it shares with the CPU
     test program and the kernels' header it shares with mdc_pngdx.hip, independent of every other library here and outside
     libmdc_hip.so's build identity.  The dataset reader loads it at run time (csrc/host/device_lanes.cpp), nothing links it."""
-    if force or _stale(LIB_PNGD, [PNGD_SOURCE, PNGD_CORE, PNG_DECODE_KERNELS, os.path.join(INC, "mdc_pngd.h"), PNGD_EXPORT_MAP]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, PNGD_SOURCE, "-Wl,--version-script=" + PNGD_EXPORT_MAP, "-o", LIB_PNGD])
-    return LIB_PNGD
+    return _build_codec(LIB_PNGD, PNGD_SOURCE, [PNGD_CORE, PNG_DECODE_KERNELS, os.path.join(INC, "mdc_pngd.h")], PNGD_EXPORT_MAP, force=force)
 
 
 def build_pngd_core_program(out, sanitize=True):
     """tests/native/pngd_core.cpp: png_inflate_core.h as a stand-alone program (its own main), under AddressSanitizer and
     UndefinedBehaviorSanitizer (tests/test_pngd_cpu.py).  Pure host code: no HIP, no library of ours."""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
-    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pngd_core.cpp"), "-o", out])
-    return out
+    return _build_native_program("pngd_core.cpp", out, sanitize)
 
 
 LIB_PNGDX = os.path.join(PKG, "libmdc_pngdx.so")
@@ -396,18 +395,13 @@ def build_pngdx(force=False):
     translation unit, the kernels' header it shares with mdc_pngd.hip and the two core headers it shares with the CPU test programs;
     it links neither libmdc_pngd.so nor libmdc_hip.so and is outside the product's build identity.  The dataset reader loads it at
     run time when MDC_GPU_PNG=3 asks for it."""
-    if force or _stale(LIB_PNGDX, [PNGDX_SOURCE, PNGD_CORE, PNGDX_CORE, PNG_DECODE_KERNELS, os.path.join(INC, "mdc_pngdx.h"), PNGDX_EXPORT_MAP]):
-        _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-              "-Wall", "-I" + INC, PNGDX_SOURCE, "-Wl,--version-script=" + PNGDX_EXPORT_MAP, "-o", LIB_PNGDX])
-    return LIB_PNGDX
+    return _build_codec(LIB_PNGDX, PNGDX_SOURCE, [PNGD_CORE, PNGDX_CORE, PNG_DECODE_KERNELS, os.path.join(INC, "mdc_pngdx.h")], PNGDX_EXPORT_MAP, force=force)
 
 
 def build_pngdx_core_program(out, sanitize=True):
     """tests/native/pngdx_core.cpp: png_tokens_core.h (the token path of libmdc_pngdx.so) as a stand-alone program (its own main),
     under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_pngdx_cpu.py).  Pure host code: no HIP, no library of ours."""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
-    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", "pngdx_core.cpp"), "-o", out])
-    return out
+    return _build_native_program("pngdx_core.cpp", out, sanitize)
 
 
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")

@@ -385,15 +385,6 @@ LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
 LIB_PNGDX_PATH = os.path.join(_PKG, "libmdc_pngdx.so")
 _hip = None
 _host = None
-_bench = None
-_jenc = None
-_jopt = None
-_zipw = None
-_pngw = None
-_pngw_rgb = None
-_pnglz = None
-_pngd = None
-_pngdx = None
 
 
 def _share_hip_runtime_with_torch():
@@ -431,85 +422,31 @@ def _load(path, table, product=True):
     return _bind(C.CDLL(path), table, product)
 
 
-def bench_lib():
-    """libmdc_bench.so: the synthetic sequence generator and the linear-stream yardstick (bench.py, tools/, tests/)."""
-    global _bench
-    if _bench is None:
-        _share_hip_runtime_with_torch()
-        _bench = _load(LIB_BENCH_PATH, BENCH_API)
-    return _bench
+def _lazy_lib(path, table, doc):
+    """An accessor that loads the library at `path` with the functions of `table` at its first call and returns the same object
+    ever after."""
+    cache = []
+
+    def lib():
+        if not cache:
+            _share_hip_runtime_with_torch()
+            cache.append(_load(path, table))
+        return cache[0]
+
+    lib.__doc__ = doc
+    return lib
 
 
-def jenc_lib():
-    """libmdc_jenc.so: the baseline JPEG encoder for device-resident frames (include/mdc_jenc.h)."""
-    global _jenc
-    if _jenc is None:
-        _share_hip_runtime_with_torch()
-        _jenc = _load(LIB_JENC_PATH, JENC_API)
-    return _jenc
-
-
-def jopt_lib():
-    """libmdc_jopt.so: the JPEG encoder with one optimal Huffman table pair per frame (include/mdc_jopt.h)."""
-    global _jopt
-    if _jopt is None:
-        _share_hip_runtime_with_torch()
-        _jopt = _load(LIB_JOPT_PATH, JOPT_API)
-    return _jopt
-
-
-def zipw_lib():
-    """libmdc_zipw.so: CRC-32, ZIP segments and the archive writer for device-resident files (include/mdc_zipw.h)."""
-    global _zipw
-    if _zipw is None:
-        _share_hip_runtime_with_torch()
-        _zipw = _load(LIB_ZIPW_PATH, ZIPW_API)
-    return _zipw
-
-
-def pngw_lib():
-    """libmdc_pngw.so: the PNG encoder for device-resident grayscale images (include/mdc_pngw.h)."""
-    global _pngw
-    if _pngw is None:
-        _share_hip_runtime_with_torch()
-        _pngw = _load(LIB_PNGW_PATH, PNGW_API)
-    return _pngw
-
-
-def pngw_rgb_lib():
-    """libmdc_pngw_rgb.so: the PNG encoder for device-resident 8-bit RGB images (include/mdc_pngw_rgb.h)."""
-    global _pngw_rgb
-    if _pngw_rgb is None:
-        _share_hip_runtime_with_torch()
-        _pngw_rgb = _load(LIB_PNGW_RGB_PATH, PNGW_RGB_API)
-    return _pngw_rgb
-
-
-def pnglz_lib():
-    """libmdc_pnglz.so: the PNG encoder with LZ77 matches for device-resident gray and RGB images (include/mdc_pnglz.h)."""
-    global _pnglz
-    if _pnglz is None:
-        _share_hip_runtime_with_torch()
-        _pnglz = _load(LIB_PNGLZ_PATH, PNGLZ_API)
-    return _pnglz
-
-
-def pngd_lib():
-    """libmdc_pngd.so: the PNG decoder for frames whose zlib streams are in device or host memory (include/mdc_pngd.h)."""
-    global _pngd
-    if _pngd is None:
-        _share_hip_runtime_with_torch()
-        _pngd = _load(LIB_PNGD_PATH, PNGD_API)
-    return _pngd
-
-
-def pngdx_lib():
-    """libmdc_pngdx.so: the PNG decoder with a parallel inflate for streams with matches (include/mdc_pngdx.h)."""
-    global _pngdx
-    if _pngdx is None:
-        _share_hip_runtime_with_torch()
-        _pngdx = _load(LIB_PNGDX_PATH, PNGDX_API)
-    return _pngdx
+bench_lib = _lazy_lib(LIB_BENCH_PATH, BENCH_API, "libmdc_bench.so: the synthetic sequence generator and the linear-stream yardstick (bench.py, tools/, tests/).")
+jenc_lib = _lazy_lib(LIB_JENC_PATH, JENC_API, "libmdc_jenc.so: the baseline JPEG encoder for device-resident frames (include/mdc_jenc.h).")
+jopt_lib = _lazy_lib(LIB_JOPT_PATH, JOPT_API, "libmdc_jopt.so: the JPEG encoder with one optimal Huffman table pair per frame (include/mdc_jopt.h).")
+zipw_lib = _lazy_lib(LIB_ZIPW_PATH, ZIPW_API, "libmdc_zipw.so: CRC-32, ZIP segments and the archive writer for device-resident files (include/mdc_zipw.h).")
+pngw_lib = _lazy_lib(LIB_PNGW_PATH, PNGW_API, "libmdc_pngw.so: the PNG encoder for device-resident grayscale images (include/mdc_pngw.h).")
+pngw_rgb_lib = _lazy_lib(LIB_PNGW_RGB_PATH, PNGW_RGB_API, "libmdc_pngw_rgb.so: the PNG encoder for device-resident 8-bit RGB images (include/mdc_pngw_rgb.h).")
+pnglz_lib = _lazy_lib(LIB_PNGLZ_PATH, PNGLZ_API,
+                      "libmdc_pnglz.so: the PNG encoder with LZ77 matches for device-resident gray and RGB images (include/mdc_pnglz.h).")
+pngd_lib = _lazy_lib(LIB_PNGD_PATH, PNGD_API, "libmdc_pngd.so: the PNG decoder for frames whose zlib streams are in device or host memory (include/mdc_pngd.h).")
+pngdx_lib = _lazy_lib(LIB_PNGDX_PATH, PNGDX_API, "libmdc_pngdx.so: the PNG decoder with a parallel inflate for streams with matches (include/mdc_pngdx.h).")
 
 
 def hip_lib():

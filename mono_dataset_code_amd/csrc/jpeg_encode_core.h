@@ -1,16 +1,20 @@
 // jpeg_encode_core.h -- what the two device JPEG encoder libraries share, one copy of the source: mdc_jenc.hip (libmdc_jenc.so, the
 // Annex K tables) and mdc_jopt.hip (libmdc_jopt.so, one optimal table pair per frame).  The constant tables, the forward DCT and
 // quantisation kernel, the block walker with its bit counter and bit packer, the per-frame scan, the gather kernel of the fetch
-// call, and the host helpers.  Each library is one translation unit and includes this once; everything is in its unnamed namespace.
+// call, and the host side of both libraries, which each parametrises with a Params.  Each library is one translation unit and
+// includes this once; everything is in its unnamed namespace.  (The two stuffing kernels differ only in their header lines and
+// stay two copies: with the loop in a function here, both compiled to other instructions.)
 #ifndef MDC_JPEG_ENCODE_CORE_H
 #define MDC_JPEG_ENCODE_CORE_H
 
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
+
+#include <new>
+
+#include "codec_host.h"
 
 namespace {
 
@@ -264,30 +268,6 @@ __global__ __launch_bounds__(256) void jenc_gather_kernel(const uint8_t* __restr
 
 // ---------------------------------------------------------------------------------------------------- host side
 
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 void huffman_table(const uint8_t* bits, const uint8_t* vals, uint32_t* out) {  // Annex C: canonical codes
   uint32_t code = 0;
   int k = 0;
@@ -334,6 +314,179 @@ void fill_tables(DeviceTables* t, int w, int h, int quality) {
 }
 
 long long blocks_of(int w, int h) { return (long long)((w + 7) / 8) * ((h + 7) / 8); }
+
+// What tells the two libraries' host sides apart, beside the launch sequence of an encode call
+struct Params {
+  const char* prefix;      // of the functions' names in messages: "mdcj", "mdcjo"
+  int bound_per_block;     // *_jpeg_bound: 1024 + this many bytes per block
+  int bits_per_block_max;  // the longest code of a block (the public header derives it)
+};
+
+// The fields both encoders have.  struct mdcj_encoder and struct mdcjo_encoder derive from it; each adds alloc_extra() and
+// free_extra() for what it has beyond them (called with the encoder's device current).
+struct Encoder {
+  int device = -1, w = 0, h = 0, quality = 0, max_frames = 0;
+  int nblocks = 0;
+  long long stream_words = 0;  // per frame
+  DeviceTables* d_tab = nullptr;
+  int16_t* d_coef = nullptr;
+  uint32_t* d_bits = nullptr;
+  uint32_t* d_frame_bits = nullptr;
+  uint32_t* d_stream = nullptr;
+  uint8_t* d_out = nullptr;  // output_device: allocated on demand
+  int32_t* d_sizes = nullptr;
+  uint8_t* d_packed = nullptr;  // fetch: the files back to back (grown on demand) and their offsets
+  long long packed_capacity = 0;
+  long long* d_offsets = nullptr;
+};
+
+int64_t jpeg_bound(const Params& p, int w, int h) {
+  if (w < 1 || h < 1 || w > 65535 || h > 65535) return -1;
+  return 1024 + p.bound_per_block * blocks_of(w, h);
+}
+
+template <class E>
+void destroy(E* enc) {
+  if (!enc) return;
+  {
+    DeviceGuard dg(enc->device);
+    (void)hipFree(enc->d_tab);
+    (void)hipFree(enc->d_coef);
+    (void)hipFree(enc->d_bits);
+    (void)hipFree(enc->d_frame_bits);
+    (void)hipFree(enc->d_stream);
+    enc->free_extra();
+    (void)hipFree(enc->d_out);
+    (void)hipFree(enc->d_sizes);
+    (void)hipFree(enc->d_packed);
+    (void)hipFree(enc->d_offsets);
+  }
+  delete enc;
+}
+
+template <class E>
+int create(const char* who, const Params& p, int device, int w, int h, int quality, int max_frames, E** out) {
+  if (!out) return fail(kErrArg, "%s: out is null", who);
+  *out = nullptr;
+  if (w < 1 || h < 1 || w > 65535 || h > 65535) return fail(kErrSize, "%s: %d x %d is outside 1..65535 (the SOF0 fields are 16-bit)", who, w, h);
+  if (quality < 1 || quality > 100) return fail(kErrArg, "%s: quality %d is outside 1..100", who, quality);
+  if (max_frames < 1) return fail(kErrArg, "%s: max_frames %d is below 1", who, max_frames);
+  const long long nblocks = blocks_of(w, h);
+  if (jpeg_bound(p, w, h) > (1ll << 30))
+    return fail(kErrSize, "%s: %d x %d has %lld blocks; a frame's bit offsets are 32-bit (bound <= 2^30)", who, w, h, nblocks);
+  if (nblocks * max_frames > 0x7fffffffll) return fail(kErrSize, "%s: %lld blocks x %d frames per call is 2^31 or more", who, nblocks, max_frames);
+  if (int rc = resolve_device(who, &device)) return rc;
+  DeviceGuard dg(device);
+  E* e = new (std::nothrow) E;
+  if (!e) return fail(kErrNoMem, "%s: out of host memory", who);
+  e->device = device, e->w = w, e->h = h, e->quality = quality, e->max_frames = max_frames;
+  e->nblocks = (int)nblocks;
+  // ceil(bits_per_block_max * nblocks / 32) words hold the longest stream; jenc_scan_kernel clears up to two more
+  e->stream_words = ((long long)p.bits_per_block_max * nblocks + 31) / 32 + 2;
+  const size_t n = (size_t)nblocks * (size_t)max_frames;
+  if (hipMalloc((void**)&e->d_tab, sizeof(DeviceTables)) != hipSuccess || hipMalloc((void**)&e->d_coef, n * 64 * sizeof(int16_t)) != hipSuccess ||
+      hipMalloc((void**)&e->d_bits, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&e->d_frame_bits, (size_t)max_frames * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc((void**)&e->d_stream, (size_t)e->stream_words * (size_t)max_frames * sizeof(uint32_t)) != hipSuccess || !e->alloc_extra()) {
+    (void)hipGetLastError();
+    destroy(e);
+    return fail(kErrNoMem, "%s: could not allocate the scratch arrays of %d frames of %d x %d", who, max_frames, w, h);
+  }
+  DeviceTables tab;
+  fill_tables(&tab, w, h, quality);
+  if (hipMemcpy(e->d_tab, &tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
+    destroy(e);
+    return fail(kErrHip, "%s: copying the tables failed", who);
+  }
+  *out = e;
+  return kOk;
+}
+
+// The argument checks of an encode call.  *go: there are frames to encode.
+int check_encode(const char* who, const Params& p, const Encoder* e, const void* d_frames, int64_t frame_stride, int nframes, const uint8_t* d_out, int64_t slot_bytes,
+                 const int32_t* d_sizes, bool* go) {
+  *go = false;
+  if (!e) return fail(kErrArg, "%s: encoder is null", who);
+  if (nframes < 0 || nframes > e->max_frames) return fail(kErrArg, "%s: %d frames, the encoder was made for 0..%d", who, nframes, e->max_frames);
+  if (nframes == 0) return kOk;
+  if (!d_frames || !d_out || !d_sizes) return fail(kErrArg, "%s: null device pointer", who);
+  if (frame_stride < (int64_t)e->w * e->h) return fail(kErrArg, "%s: frame_stride %lld is below %d x %d", who, (long long)frame_stride, e->w, e->h);
+  const int64_t bound = jpeg_bound(p, e->w, e->h);
+  if (slot_bytes < bound)
+    return fail(kErrSize, "%s: slot_bytes %lld is below %s_jpeg_bound(%d, %d) = %lld", who, (long long)slot_bytes, p.prefix, e->w, e->h, (long long)bound);
+  *go = true;
+  return kOk;
+}
+
+int output_device(const Params& p, Encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
+  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(kErrArg, "%s_output_device: null argument", p.prefix);
+  const int64_t bound = jpeg_bound(p, enc->w, enc->h);
+  if (!enc->d_out) {
+    DeviceGuard dg(enc->device);
+    uint8_t* o = nullptr;
+    int32_t* z = nullptr;
+    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_frames) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_frames * sizeof(int32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(o);
+      return fail(kErrNoMem, "%s_output_device: could not allocate %d slots of %lld bytes", p.prefix, enc->max_frames, (long long)bound);
+    }
+    enc->d_out = o, enc->d_sizes = z;
+  }
+  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
+  return kOk;
+}
+
+int64_t fetch(const Params& p, Encoder* enc, const uint8_t* d_out, int64_t slot_bytes, const int32_t* d_sizes, int nframes, uint8_t* h_out, int64_t h_capacity,
+              int32_t* h_sizes, void* stream) {
+  if (!enc || !d_out || !d_sizes || !h_sizes) return fail(kErrArg, "%s_fetch: null argument", p.prefix);
+  if (nframes < 0 || nframes > enc->max_frames) return fail(kErrArg, "%s_fetch: %d frames, the encoder was made for 0..%d", p.prefix, nframes, enc->max_frames);
+  if (nframes == 0) return 0;
+  DeviceGuard dg(enc->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(h_sizes, d_sizes, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return fail(kErrHip, "%s_fetch: copying the sizes failed: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+  int64_t total = 0;
+  for (int f = 0; f < nframes; f++) {
+    if (h_sizes[f] <= 0 || h_sizes[f] > slot_bytes)
+      return fail(kErrSize, "%s_fetch: frame %d has size %d, the slot %lld", p.prefix, f, h_sizes[f], (long long)slot_bytes);
+    total += h_sizes[f];
+  }
+  if (!h_out) return total;
+  if (total > h_capacity) return fail(kErrSize, "%s_fetch: %lld bytes, room for %lld", p.prefix, (long long)total, (long long)h_capacity);
+  // one copy per file costs more than the bytes (a thousand copies of 100 KB): gather on the device, copy once
+  if (total > enc->packed_capacity || !enc->d_offsets) {
+    (void)hipFree(enc->d_packed);
+    enc->d_packed = nullptr, enc->packed_capacity = 0;
+    const long long want = total + total / 4 + 4096;
+    if (hipMalloc((void**)&enc->d_packed, (size_t)want) != hipSuccess ||
+        (!enc->d_offsets && hipMalloc((void**)&enc->d_offsets, ((size_t)enc->max_frames + 1) * sizeof(long long)) != hipSuccess)) {
+      (void)hipGetLastError();
+      return fail(kErrNoMem, "%s_fetch: could not allocate %lld bytes for the gathered files", p.prefix, want);
+    }
+    enc->packed_capacity = want;
+  }
+  long long* offsets = new (std::nothrow) long long[(size_t)nframes + 1];
+  if (!offsets) return fail(kErrNoMem, "%s_fetch: out of host memory", p.prefix);
+  long long at = 0;
+  int largest = 0;
+  for (int f = 0; f < nframes; f++) {
+    offsets[f] = at;
+    at += h_sizes[f];
+    if (h_sizes[f] > largest) largest = h_sizes[f];
+  }
+  offsets[nframes] = at;
+  hipError_t err = hipMemcpy(enc->d_offsets, offsets, ((size_t)nframes + 1) * sizeof(long long), hipMemcpyHostToDevice);
+  delete[] offsets;
+  if (err != hipSuccess) return fail(kErrHip, "%s_fetch: copying the offsets failed: %s", p.prefix, hipGetErrorString(err));
+  const unsigned parts = (unsigned)((largest + 16 * 256 - 1) / (16 * 256));  // 16 bytes per thread
+  for (int f0 = 0; f0 < nframes; f0 += 65535) {
+    const unsigned nf = (unsigned)(nframes - f0 < 65535 ? nframes - f0 : 65535);
+    jenc_gather_kernel<<<dim3(parts, nf), 256, 0, s>>>(d_out + (int64_t)f0 * slot_bytes, (long long)slot_bytes, enc->d_offsets + f0, enc->d_packed);
+  }
+  if ((err = hipGetLastError()) != hipSuccess || (err = hipMemcpyAsync(h_out, enc->d_packed, (size_t)total, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (err = hipStreamSynchronize(s)) != hipSuccess)
+    return fail(kErrHip, "%s_fetch: gathering the files failed: %s", p.prefix, hipGetErrorString(err));
+  return total;
+}
 
 }  // namespace
 

@@ -19,11 +19,9 @@
 #include "jpeg_encode_core.h"
 #include "jpeg_optimal_table.h"
 
-#include <new>
-
 namespace {
 
-constexpr int kBitsPerBlockMax = 27 + 63 * 26;  // include/mdc_jopt.h: the bound's derivation
+constexpr Params kParams = {"mdcjo", 418, 27 + 63 * 26};  // include/mdc_jopt.h: the bound's derivation
 constexpr int kPrefixBytes = 20 + 5 + 64 + 13;  // SOI, APP0, DQT, SOF0: the same for every frame of an encoder
 constexpr int kSosBytes = 10;
 constexpr int kDhtMax = 5 + 16 + 256;  // marker, length, class / id, the 16 counts, the symbols
@@ -271,112 +269,34 @@ __global__ __launch_bounds__(1024) void jopt_stuff_kernel(const uint32_t* __rest
 
 }  // namespace
 
-struct mdcjo_encoder {
-  int device = -1, w = 0, h = 0, quality = 0, max_frames = 0;
-  int nblocks = 0;
-  long long stream_words = 0;  // per frame
-  DeviceTables* d_tab = nullptr;
-  int16_t* d_coef = nullptr;
-  uint32_t* d_bits = nullptr;
-  uint32_t* d_frame_bits = nullptr;
-  uint32_t* d_stream = nullptr;
-  uint32_t* d_hist = nullptr;            // per frame uint32[2][257]
-  FrameTables* d_frame_tab = nullptr;    // per frame
-  uint8_t* d_out = nullptr;  // mdcjo_output_device: allocated on demand
-  int32_t* d_sizes = nullptr;
-  uint8_t* d_packed = nullptr;  // mdcjo_fetch: the files back to back (grown on demand) and their offsets
-  long long packed_capacity = 0;
-  long long* d_offsets = nullptr;
+static_assert(MDCJO_OK == kOk && MDCJO_ERR_ARG == kErrArg && MDCJO_ERR_SIZE == kErrSize && MDCJO_ERR_HIP == kErrHip && MDCJO_ERR_NO_DEVICE == kErrNoDevice &&
+                  MDCJO_ERR_NOMEM == kErrNoMem,
+              "include/mdc_jopt.h and codec_host.h name the same codes");
+
+struct mdcjo_encoder : Encoder {
+  uint32_t* d_hist = nullptr;          // per frame uint32[2][257]
+  FrameTables* d_frame_tab = nullptr;  // per frame
   bool profile = false, timed = false;
   hipEvent_t ev[MDCJO_KERNELS + 1] = {};
-};
-
-extern "C" {
-
-int64_t mdcjo_jpeg_bound(int w, int h) {
-  if (w < 1 || h < 1 || w > 65535 || h > 65535) return -1;
-  return 1024 + 418 * blocks_of(w, h);
-}
-
-const char* mdcjo_last_error(void) { return g_error; }
-
-void mdcjo_destroy(mdcjo_encoder* enc) {
-  if (!enc) return;
-  {
-    DeviceGuard dg(enc->device);
-    (void)hipFree(enc->d_tab);
-    (void)hipFree(enc->d_coef);
-    (void)hipFree(enc->d_bits);
-    (void)hipFree(enc->d_frame_bits);
-    (void)hipFree(enc->d_stream);
-    (void)hipFree(enc->d_hist);
-    (void)hipFree(enc->d_frame_tab);
-    (void)hipFree(enc->d_out);
-    (void)hipFree(enc->d_sizes);
-    (void)hipFree(enc->d_packed);
-    (void)hipFree(enc->d_offsets);
-    for (hipEvent_t e : enc->ev)
+  bool alloc_extra() {
+    return hipMalloc((void**)&d_hist, (size_t)max_frames * kHistWords * sizeof(uint32_t)) == hipSuccess &&
+           hipMalloc((void**)&d_frame_tab, (size_t)max_frames * sizeof(FrameTables)) == hipSuccess;
+  }
+  void free_extra() {
+    (void)hipFree(d_hist);
+    (void)hipFree(d_frame_tab);
+    for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
-  delete enc;
-}
-
-int mdcjo_create(int device, int w, int h, int quality, int max_frames, mdcjo_encoder** out) {
-  if (!out) return fail(MDCJO_ERR_ARG, "mdcjo_create: out is null");
-  *out = nullptr;
-  if (w < 1 || h < 1 || w > 65535 || h > 65535) return fail(MDCJO_ERR_SIZE, "mdcjo_create: %d x %d is outside 1..65535 (the SOF0 fields are 16-bit)", w, h);
-  if (quality < 1 || quality > 100) return fail(MDCJO_ERR_ARG, "mdcjo_create: quality %d is outside 1..100", quality);
-  if (max_frames < 1) return fail(MDCJO_ERR_ARG, "mdcjo_create: max_frames %d is below 1", max_frames);
-  const long long nblocks = blocks_of(w, h);
-  if (mdcjo_jpeg_bound(w, h) > (1ll << 30))
-    return fail(MDCJO_ERR_SIZE, "mdcjo_create: %d x %d has %lld blocks; a frame's bit offsets are 32-bit (bound <= 2^30)", w, h, nblocks);
-  if (nblocks * max_frames > 0x7fffffffll)
-    return fail(MDCJO_ERR_SIZE, "mdcjo_create: %lld blocks x %d frames per call is 2^31 or more", nblocks, max_frames);
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MDCJO_ERR_NO_DEVICE, "mdcjo_create: no HIP device");
-  if (device >= count) return fail(MDCJO_ERR_NO_DEVICE, "mdcjo_create: device %d of %d", device, count);
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(MDCJO_ERR_HIP, "mdcjo_create: hipGetDevice failed");
-  DeviceGuard dg(device);
-  mdcjo_encoder* e = new (std::nothrow) mdcjo_encoder;
-  if (!e) return fail(MDCJO_ERR_NOMEM, "mdcjo_create: out of host memory");
-  e->device = device, e->w = w, e->h = h, e->quality = quality, e->max_frames = max_frames;
-  e->nblocks = (int)nblocks;
-  // ceil(1665 * nblocks / 32) words hold the longest stream; jenc_scan_kernel clears up to two more
-  e->stream_words = ((long long)kBitsPerBlockMax * nblocks + 31) / 32 + 2;
-  const size_t n = (size_t)nblocks * (size_t)max_frames;
-  if (hipMalloc((void**)&e->d_tab, sizeof(DeviceTables)) != hipSuccess || hipMalloc((void**)&e->d_coef, n * 64 * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void**)&e->d_bits, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&e->d_frame_bits, (size_t)max_frames * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&e->d_stream, (size_t)e->stream_words * (size_t)max_frames * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&e->d_hist, (size_t)max_frames * kHistWords * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&e->d_frame_tab, (size_t)max_frames * sizeof(FrameTables)) != hipSuccess) {
-    (void)hipGetLastError();
-    mdcjo_destroy(e);
-    return fail(MDCJO_ERR_NOMEM, "mdcjo_create: could not allocate the scratch arrays of %d frames of %d x %d", max_frames, w, h);
-  }
-  DeviceTables tab;
-  fill_tables(&tab, w, h, quality);
-  if (hipMemcpy(e->d_tab, &tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
-    mdcjo_destroy(e);
-    return fail(MDCJO_ERR_HIP, "mdcjo_create: copying the tables failed");
-  }
-  *out = e;
-  return MDCJO_OK;
-}
-
-}  // extern "C"
+};
 
 namespace {
 
 template <typename T>
 int encode(const char* who, mdcjo_encoder* e, const T* d_frames, int64_t frame_stride, int nframes, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes,
            void* stream) {
-  if (!e) return fail(MDCJO_ERR_ARG, "%s: encoder is null", who);
-  if (nframes < 0 || nframes > e->max_frames) return fail(MDCJO_ERR_ARG, "%s: %d frames, the encoder was made for 0..%d", who, nframes, e->max_frames);
-  if (nframes == 0) return MDCJO_OK;
-  if (!d_frames || !d_out || !d_sizes) return fail(MDCJO_ERR_ARG, "%s: null device pointer", who);
-  if (frame_stride < (int64_t)e->w * e->h) return fail(MDCJO_ERR_ARG, "%s: frame_stride %lld is below %d x %d", who, (long long)frame_stride, e->w, e->h);
-  const int64_t bound = mdcjo_jpeg_bound(e->w, e->h);
-  if (slot_bytes < bound) return fail(MDCJO_ERR_SIZE, "%s: slot_bytes %lld is below mdcjo_jpeg_bound(%d, %d) = %lld", who, (long long)slot_bytes, e->w, e->h, (long long)bound);
+  bool go;
+  if (int rc = check_encode(who, kParams, e, d_frames, frame_stride, nframes, d_out, slot_bytes, d_sizes, &go); rc || !go) return rc;
   DeviceGuard dg(e->device);
   hipStream_t s = (hipStream_t)stream;
   const int nblocks = e->nblocks, bw = (e->w + 7) / 8;
@@ -422,6 +342,16 @@ int encode(const char* who, mdcjo_encoder* e, const T* d_frames, int64_t frame_s
 
 extern "C" {
 
+int64_t mdcjo_jpeg_bound(int w, int h) { return jpeg_bound(kParams, w, h); }
+
+const char* mdcjo_last_error(void) { return g_error; }
+
+void mdcjo_destroy(mdcjo_encoder* enc) { destroy(enc); }
+
+int mdcjo_create(int device, int w, int h, int quality, int max_frames, mdcjo_encoder** out) {
+  return create("mdcjo_create", kParams, device, w, h, quality, max_frames, out);
+}
+
 int mdcjo_encode_f32_device(mdcjo_encoder* enc, const float* d_frames, int64_t frame_stride, int nframes, uint8_t* d_out, int64_t slot_bytes, int32_t* d_sizes,
                             void* stream) {
   return encode("mdcjo_encode_f32_device", enc, d_frames, frame_stride, nframes, d_out, slot_bytes, d_sizes, stream);
@@ -445,74 +375,11 @@ int mdcjo_optimal_tables_device(mdcjo_encoder* enc, const uint32_t* d_freq, int 
   return MDCJO_OK;
 }
 
-int mdcjo_output_device(mdcjo_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) {
-  if (!enc || !d_out || !slot_bytes || !d_sizes) return fail(MDCJO_ERR_ARG, "mdcjo_output_device: null argument");
-  const int64_t bound = mdcjo_jpeg_bound(enc->w, enc->h);
-  if (!enc->d_out) {
-    DeviceGuard dg(enc->device);
-    uint8_t* o = nullptr;
-    int32_t* z = nullptr;
-    if (hipMalloc((void**)&o, (size_t)bound * (size_t)enc->max_frames) != hipSuccess || hipMalloc((void**)&z, (size_t)enc->max_frames * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(o);
-      return fail(MDCJO_ERR_NOMEM, "mdcjo_output_device: could not allocate %d slots of %lld bytes", enc->max_frames, (long long)bound);
-    }
-    enc->d_out = o, enc->d_sizes = z;
-  }
-  *d_out = enc->d_out, *slot_bytes = bound, *d_sizes = enc->d_sizes;
-  return MDCJO_OK;
-}
+int mdcjo_output_device(mdcjo_encoder* enc, uint8_t** d_out, int64_t* slot_bytes, int32_t** d_sizes) { return output_device(kParams, enc, d_out, slot_bytes, d_sizes); }
 
 int64_t mdcjo_fetch(mdcjo_encoder* enc, const uint8_t* d_out, int64_t slot_bytes, const int32_t* d_sizes, int nframes, uint8_t* h_out, int64_t h_capacity,
                     int32_t* h_sizes, void* stream) {
-  if (!enc || !d_out || !d_sizes || !h_sizes) return fail(MDCJO_ERR_ARG, "mdcjo_fetch: null argument");
-  if (nframes < 0 || nframes > enc->max_frames) return fail(MDCJO_ERR_ARG, "mdcjo_fetch: %d frames, the encoder was made for 0..%d", nframes, enc->max_frames);
-  if (nframes == 0) return 0;
-  DeviceGuard dg(enc->device);
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpyAsync(h_sizes, d_sizes, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return fail(MDCJO_ERR_HIP, "mdcjo_fetch: copying the sizes failed: %s", hipGetErrorString(hipGetLastError()));
-  int64_t total = 0;
-  for (int f = 0; f < nframes; f++) {
-    if (h_sizes[f] <= 0 || h_sizes[f] > slot_bytes) return fail(MDCJO_ERR_SIZE, "mdcjo_fetch: frame %d has size %d, the slot %lld", f, h_sizes[f], (long long)slot_bytes);
-    total += h_sizes[f];
-  }
-  if (!h_out) return total;
-  if (total > h_capacity) return fail(MDCJO_ERR_SIZE, "mdcjo_fetch: %lld bytes, room for %lld", (long long)total, (long long)h_capacity);
-  // one copy per file costs more than the bytes: gather on the device, copy once
-  if (total > enc->packed_capacity || !enc->d_offsets) {
-    (void)hipFree(enc->d_packed);
-    enc->d_packed = nullptr, enc->packed_capacity = 0;
-    const long long want = total + total / 4 + 4096;
-    if (hipMalloc((void**)&enc->d_packed, (size_t)want) != hipSuccess ||
-        (!enc->d_offsets && hipMalloc((void**)&enc->d_offsets, ((size_t)enc->max_frames + 1) * sizeof(long long)) != hipSuccess)) {
-      (void)hipGetLastError();
-      return fail(MDCJO_ERR_NOMEM, "mdcjo_fetch: could not allocate %lld bytes for the gathered files", want);
-    }
-    enc->packed_capacity = want;
-  }
-  long long* offsets = new (std::nothrow) long long[(size_t)nframes + 1];
-  if (!offsets) return fail(MDCJO_ERR_NOMEM, "mdcjo_fetch: out of host memory");
-  long long at = 0;
-  int largest = 0;
-  for (int f = 0; f < nframes; f++) {
-    offsets[f] = at;
-    at += h_sizes[f];
-    if (h_sizes[f] > largest) largest = h_sizes[f];
-  }
-  offsets[nframes] = at;
-  hipError_t err = hipMemcpy(enc->d_offsets, offsets, ((size_t)nframes + 1) * sizeof(long long), hipMemcpyHostToDevice);
-  delete[] offsets;
-  if (err != hipSuccess) return fail(MDCJO_ERR_HIP, "mdcjo_fetch: copying the offsets failed: %s", hipGetErrorString(err));
-  const unsigned parts = (unsigned)((largest + 16 * 256 - 1) / (16 * 256));  // 16 bytes per thread
-  for (int f0 = 0; f0 < nframes; f0 += 65535) {
-    const unsigned nf = (unsigned)(nframes - f0 < 65535 ? nframes - f0 : 65535);
-    jenc_gather_kernel<<<dim3(parts, nf), 256, 0, s>>>(d_out + (int64_t)f0 * slot_bytes, (long long)slot_bytes, enc->d_offsets + f0, enc->d_packed);
-  }
-  if ((err = hipGetLastError()) != hipSuccess || (err = hipMemcpyAsync(h_out, enc->d_packed, (size_t)total, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (err = hipStreamSynchronize(s)) != hipSuccess)
-    return fail(MDCJO_ERR_HIP, "mdcjo_fetch: gathering the files failed: %s", hipGetErrorString(err));
-  return total;
+  return fetch(kParams, enc, d_out, slot_bytes, d_sizes, nframes, h_out, h_capacity, h_sizes, stream);
 }
 
 int mdcjo_profile(mdcjo_encoder* enc, int on) {

@@ -31,8 +31,8 @@
 
 namespace {
 
-static_assert(MDCL_ERR_ARG == kErrArg && MDCL_ERR_NOMEM == kErrNoMem && MDCL_OK == 0,
-              "png_encode_core.h restates these values of include/mdc_pnglz.h");
+static_assert(MDCL_OK == kOk && MDCL_ERR_ARG == kErrArg && MDCL_ERR_HIP == kErrHip && MDCL_ERR_NO_DEVICE == kErrNoDevice && MDCL_ERR_NOMEM == kErrNoMem,
+              "codec_host.h restates these values of include/mdc_pnglz.h");
 
 constexpr int kHistAt = 0;                    // per image, cleared per call: the filtered bytes' histogram [256]
 constexpr int kAdlerAt = 256;                 //   the Adler sums as two 64-bit words
@@ -639,10 +639,7 @@ int mdcl_create(int device, int w, int h, int kind, int filter, int chain, int m
   const long long per_image = 152 * nunits + kSmallBytes;
   if (per_image > (1ll << 40) / max_images)
     return fail(MDCL_ERR_SIZE, "%s: %d images x %lld bytes of scratch pass 2^40 bytes", who, max_images, per_image);
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MDCL_ERR_NO_DEVICE, "%s: no HIP device", who);
-  if (device >= count) return fail(MDCL_ERR_NO_DEVICE, "%s: device %d of %d", who, device, count);
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(MDCL_ERR_HIP, "%s: hipGetDevice failed", who);
+  if (int rc = resolve_device(who, &device)) return rc;
   DeviceGuard dg(device);
   mdcl_encoder* e = new (std::nothrow) mdcl_encoder;
   if (!e) return fail(MDCL_ERR_NOMEM, "%s: out of host memory", who);

@@ -36,8 +36,9 @@
 
 namespace {
 
-static_assert(MDCP_MAX_SYMBOLS == kMaxSym && MDCP_ERR_ARG == kErrArg && MDCP_ERR_NOMEM == kErrNoMem && MDCP_OK == 0,
-              "png_block.h and png_encode_core.h restate these values of include/mdc_pngw.h");
+static_assert(MDCP_MAX_SYMBOLS == kMaxSym && MDCP_OK == kOk && MDCP_ERR_ARG == kErrArg && MDCP_ERR_HIP == kErrHip && MDCP_ERR_NO_DEVICE == kErrNoDevice &&
+                  MDCP_ERR_NOMEM == kErrNoMem,
+              "png_block.h and codec_host.h restate these values of include/mdc_pngw.h");
 
 constexpr int kLit = 257;            // literals and end-of-block
 constexpr int kSeq = 258;            // code lengths in the header: 257 + one distance code
@@ -413,10 +414,7 @@ int create(const char* who, int device, int w, int h, int depth, int filter, int
   const long long per_image = 24 * nunits + kSmallBytes;
   if (per_image > (1ll << 40) / max_images)
     return fail(MDCP_ERR_SIZE, "%s: %d images x %lld bytes of scratch pass 2^40 bytes", who, max_images, per_image);
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MDCP_ERR_NO_DEVICE, "%s: no HIP device", who);
-  if (device >= count) return fail(MDCP_ERR_NO_DEVICE, "%s: device %d of %d", who, device, count);
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(MDCP_ERR_HIP, "%s: hipGetDevice failed", who);
+  if (int rc = resolve_device(who, &device)) return rc;
   DeviceGuard dg(device);
   mdcp_encoder* e = new (std::nothrow) mdcp_encoder;
   if (!e) return fail(MDCP_ERR_NOMEM, "%s: out of host memory", who);

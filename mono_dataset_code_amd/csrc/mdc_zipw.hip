@@ -22,7 +22,6 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -33,6 +32,8 @@
 #include <new>
 #include <string>
 #include <vector>
+
+#include "codec_host.h"
 
 namespace {
 
@@ -371,30 +372,6 @@ __global__ __launch_bounds__(kThreads) void zipw_gather_kernel(const uint8_t* __
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-
-thread_local char g_error[320] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 int parts_for(int64_t slot_bytes, int64_t nfiles) {
   int64_t parts = (slot_bytes + (int64_t)kRowsPerPartHint * kRowBytes - 1) / ((int64_t)kRowsPerPartHint * kRowBytes);

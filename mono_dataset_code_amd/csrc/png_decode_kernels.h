@@ -1,5 +1,6 @@
 // What the two device PNG decoder libraries share (libmdc_pngd.so: mdc_pngd.hip, libmdc_pngdx.so: mdc_pngdx.hip), each of which is one
-// translation unit that includes this header once: the four kernels of libmdc_pngd.so and the host helpers around them.  Everything is in
+// translation unit that includes this header once: the four kernels of libmdc_pngd.so and the host side of both libraries, which each
+// parametrises with a Params and the launch sequence of its call.  Everything is in
 // an unnamed namespace: each library gets its own copy, neither exports any of it.
 //
 //   pngd_front_kernel     one workgroup per image: lane 0 parses the zlib header and the first block header and builds the code
@@ -18,12 +19,13 @@
 #ifndef MDC_PNG_DECODE_KERNELS_H
 #define MDC_PNG_DECODE_KERNELS_H
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
+#include <new>
+
+#include "codec_host.h"
 #include "png_inflate_core.h"
 
 namespace {
@@ -288,33 +290,219 @@ __global__ __launch_bounds__(64) void pngd_unfilter_kernel(long long nimages, in
 
 // ---------------------------------------------------------------------------------------------------- host side
 
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 int grid_for(long long items) { return (int)(items < 1 ? 1 : items > kMaxGrid ? kMaxGrid : items); }
 
 long long filt_stride_of(int w, int h) { return (((1ll + w) * h + 15) / 16) * 16; }
+
+// What tells the two libraries' host sides apart, beside the launch sequence of a call (below)
+struct Params {
+  const char* prefix;  // of the functions' names in messages: "mdci", "mdcx"
+  int extra_bytes;     // scratch per filtered byte beyond the byte itself: 0, or 4 for libmdc_pngdx.so's source indices
+  int stages;          // timed stages of a call: *_kernel_ms fills that many
+};
+constexpr int kMaxStages = 5;
+
+// The fields both decoders have.  struct mdci_decoder and struct mdcx_decoder derive from it; each adds extra(): where it keeps its own
+// scratch array of Params::extra_bytes per filtered byte, or null when it has none.
+struct Decoder {
+  int device = -1, w = 0, h = 0, max_images = 0;
+  long long F = 0, filt_stride = 0;
+  uint8_t* d_filt = nullptr;
+  uint32_t* d_meta = nullptr;
+  // decode_host: made at its first call
+  hipStream_t stream = nullptr;
+  uint8_t* h_stage = nullptr;  // pinned: n sizes (padded to 16 bytes), then n slots
+  uint8_t* d_stage = nullptr;
+  size_t stage_bytes = 0;
+  uint8_t* d_out = nullptr;
+  int32_t* d_status = nullptr;
+  // profile: events around the stages of a call, Params::stages + 1 of them
+  bool profile = false, timed = false;
+  hipEvent_t ev[kMaxStages + 1] = {};
+};
+
+// One decode_device call, as its launch sequence sees it
+struct Call {
+  Input in;
+  long long N;
+  uint8_t* frames;
+  long long frame_stride;
+  int32_t* status;
+  hipStream_t s;
+};
+
+int64_t scratch_bytes(const Params& p, int w, int h, int max_images) {
+  if (w < 1 || h < 1 || max_images < 1) return -1;
+  if ((1ll + w) > (1ll << 28) / h) return -1;
+  const long long per_image = (1 + p.extra_bytes) * filt_stride_of(w, h) + 4 * kMetaWords;
+  if (per_image > (1ll << 40) / max_images) return -1;
+  return per_image * max_images;
+}
+
+template <class D>
+void destroy(D* d) {
+  if (!d) return;
+  {
+    DeviceGuard dg(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    (void)hipFree(d->d_filt);
+    if (d->extra()) (void)hipFree(*d->extra());
+    (void)hipFree(d->d_meta);
+    (void)hipFree(d->d_stage);
+    (void)hipFree(d->d_out);
+    (void)hipFree(d->d_status);
+    if (d->h_stage) (void)hipHostFree(d->h_stage);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    for (hipEvent_t e : d->ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  delete d;
+}
+
+template <class D>
+int create(const char* who, const Params& p, int device, int w, int h, int max_images, D** out) {
+  if (!out) return fail(kErrArg, "%s: out is null", who);
+  *out = nullptr;
+  if (max_images < 1) return fail(kErrArg, "%s: max_images %d is below 1", who, max_images);
+  if (w < 1 || h < 1) return fail(kErrSize, "%s: %d x %d: width and height start at 1", who, w, h);
+  if ((1ll + w) > (1ll << 28) / h) return fail(kErrSize, "%s: a %d x %d image has more than 2^28 filtered bytes", who, w, h);
+  if (scratch_bytes(p, w, h, max_images) < 0) return fail(kErrSize, "%s: %d images of %d x %d: the scratch passes 2^40 bytes", who, max_images, w, h);
+  if (int rc = resolve_device(who, &device)) return rc;
+  DeviceGuard dg(device);
+  D* d = new (std::nothrow) D;
+  if (!d) return fail(kErrNoMem, "%s: out of host memory", who);
+  d->device = device, d->w = w, d->h = h, d->max_images = max_images;
+  d->F = (1ll + w) * h, d->filt_stride = filt_stride_of(w, h);
+  const size_t filt_bytes = (size_t)d->filt_stride * (size_t)max_images;
+  if (hipMalloc((void**)&d->d_filt, filt_bytes) != hipSuccess || (d->extra() && hipMalloc(d->extra(), filt_bytes * (size_t)p.extra_bytes) != hipSuccess) ||
+      hipMalloc((void**)&d->d_meta, (size_t)max_images * kMetaWords * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    destroy(d);
+    return fail(kErrNoMem, "%s: could not allocate the scratch arrays of %d images of %d x %d", who, max_images, w, h);
+  }
+  *out = d;
+  return kOk;
+}
+
+// launch(d, call, mark): the library's kernels of one call in order, with mark() before the first stage and after every stage
+template <class D, class Launch>
+int decode_device(const Params& p, D* d, const uint8_t* d_slots, int64_t slot_bytes, const int32_t* d_sizes, int skip_head, int skip_tail, int n, uint8_t* d_frames,
+                  int64_t frame_stride, int32_t* d_status, void* stream, Launch launch) {
+  if (!d) return fail(kErrArg, "%s_decode_device: decoder is null", p.prefix);
+  if (n < 0 || n > d->max_images) return fail(kErrArg, "%s_decode_device: %d frames, the decoder was made for 0..%d", p.prefix, n, d->max_images);
+  if (n == 0) return kOk;
+  if (!d_slots || !d_sizes || !d_frames || !d_status) return fail(kErrArg, "%s_decode_device: null device pointer", p.prefix);
+  if ((uintptr_t)d_sizes % 4 || (uintptr_t)d_status % 4) return fail(kErrArg, "%s_decode_device: d_sizes and d_status are arrays of int32_t: 4-byte aligned", p.prefix);
+  if (slot_bytes < 0) return fail(kErrArg, "%s_decode_device: slot_bytes %lld is negative", p.prefix, (long long)slot_bytes);
+  if (skip_head < 0 || skip_tail < 0) return fail(kErrArg, "%s_decode_device: skip_head %d, skip_tail %d: neither may be negative", p.prefix, skip_head, skip_tail);
+  if (frame_stride < (int64_t)d->w * d->h) return fail(kErrArg, "%s_decode_device: frame_stride %lld is below %d x %d", p.prefix, (long long)frame_stride, d->w, d->h);
+  DeviceGuard dg(d->device);
+  const Call c = {{d_slots, (long long)slot_bytes, d_sizes, skip_head, skip_tail}, n, d_frames, (long long)frame_stride, d_status, (hipStream_t)stream};
+  const bool prof = d->profile;
+  int stage = 0;
+  launch(d, c, [&]() {
+    if (prof) (void)hipEventRecord(d->ev[stage++], c.s);
+  });
+  if (prof) d->timed = true;
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(kErrHip, "%s_decode_device: launch failed: %s", p.prefix, hipGetErrorString(err));
+  return kOk;
+}
+
+int profile(const Params& p, Decoder* d, int on) {
+  if (!d) return fail(kErrArg, "%s_profile: decoder is null", p.prefix);
+  DeviceGuard dg(d->device);
+  for (int k = 0; k <= p.stages; k++)
+    if (on && !d->ev[k] && hipEventCreate(&d->ev[k]) != hipSuccess) {
+      d->ev[k] = nullptr;
+      d->profile = false;
+      return fail(kErrHip, "%s_profile: no event: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+    }
+  d->profile = on != 0;
+  d->timed = false;
+  return kOk;
+}
+
+int kernel_ms(const Params& p, Decoder* d, float* ms) {
+  if (!d || !ms) return fail(kErrArg, "%s_kernel_ms: null argument", p.prefix);
+  if (!d->timed) return fail(kErrArg, "%s_kernel_ms: no call has been timed (%s_profile, then %s_decode_device)", p.prefix, p.prefix, p.prefix);
+  DeviceGuard dg(d->device);
+  if (hipEventSynchronize(d->ev[p.stages]) != hipSuccess) return fail(kErrHip, "%s_kernel_ms: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+  for (int k = 0; k < p.stages; k++)
+    if (hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]) != hipSuccess) return fail(kErrHip, "%s_kernel_ms: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+  return kOk;
+}
+
+void* own_stream(Decoder* d) {
+  if (!d) return nullptr;
+  if (!d->stream) {
+    DeviceGuard dg(d->device);
+    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) d->stream = nullptr;
+  }
+  return d->stream;
+}
+
+int synchronize(const Params& p, Decoder* d) {
+  if (!d) return fail(kErrArg, "%s_synchronize: decoder is null", p.prefix);
+  if (!d->stream) return kOk;
+  DeviceGuard dg(d->device);
+  const hipError_t err = hipStreamSynchronize(d->stream);
+  if (err != hipSuccess) return fail(kErrHip, "%s_synchronize: %s", p.prefix, hipGetErrorString(err));
+  return kOk;
+}
+
+template <class D, class Launch>
+int decode_host(const Params& p, D* d, const void* const* streams, const int64_t* bytes, int n, int* status, const uint8_t** d_frames, Launch launch) {
+  if (!d) return fail(kErrArg, "%s_decode_host: decoder is null", p.prefix);
+  if (n < 0 || n > d->max_images) return fail(kErrArg, "%s_decode_host: %d frames, the decoder was made for 0..%d", p.prefix, n, d->max_images);
+  if (!d_frames) return fail(kErrArg, "%s_decode_host: d_frames is null", p.prefix);
+  *d_frames = d->d_out;
+  if (n == 0) return kOk;
+  if (!streams || !bytes || !status) return fail(kErrArg, "%s_decode_host: null pointer", p.prefix);
+  int64_t longest = 0;
+  for (int f = 0; f < n; f++) {
+    if (bytes[f] < 0 || bytes[f] > INT32_MAX || (bytes[f] > 0 && !streams[f])) return fail(kErrArg, "%s_decode_host: stream %d: %lld bytes at %p", p.prefix, f, (long long)bytes[f], streams[f]);
+    if (bytes[f] > longest) longest = bytes[f];
+  }
+  DeviceGuard dg(d->device);
+  const size_t head = ((size_t)n * 4 + 15) / 16 * 16, slot = ((size_t)longest + 15) / 16 * 16, need = head + slot * (size_t)n;
+  if (!own_stream(d)) return fail(kErrHip, "%s_decode_host: no stream: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+  if (!d->d_out && (hipMalloc((void**)&d->d_out, (size_t)d->max_images * d->w * d->h) != hipSuccess ||
+                    hipMalloc((void**)&d->d_status, (size_t)d->max_images * 4) != hipSuccess)) {
+    (void)hipGetLastError();
+    (void)hipFree(d->d_out);
+    d->d_out = nullptr;
+    return fail(kErrNoMem, "%s_decode_host: could not allocate %d frames of %d x %d", p.prefix, d->max_images, d->w, d->h);
+  }
+  if (need > d->stage_bytes) {
+    (void)hipStreamSynchronize(d->stream);
+    if (d->h_stage) (void)hipHostFree(d->h_stage);
+    (void)hipFree(d->d_stage);
+    d->h_stage = d->d_stage = nullptr;
+    d->stage_bytes = 0;
+    const size_t want = need + need / 4;  // some room: the next batch's longest stream is rarely the same
+    if (hipHostMalloc((void**)&d->h_stage, want, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&d->d_stage, want) != hipSuccess) {
+      (void)hipGetLastError();
+      if (d->h_stage) (void)hipHostFree(d->h_stage);
+      d->h_stage = nullptr;
+      return fail(kErrNoMem, "%s_decode_host: could not allocate %zu bytes of staging", p.prefix, want);
+    }
+    d->stage_bytes = want;
+  }
+  int32_t* sizes = (int32_t*)d->h_stage;
+  for (int f = 0; f < n; f++) {
+    sizes[f] = (int32_t)bytes[f];
+    if (bytes[f]) memcpy(d->h_stage + head + slot * (size_t)f, streams[f], (size_t)bytes[f]);
+  }
+  *d_frames = d->d_out;
+  if (hipMemcpyAsync(d->d_stage, d->h_stage, need, hipMemcpyHostToDevice, d->stream) != hipSuccess)
+    return fail(kErrHip, "%s_decode_host: upload failed: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+  const int rc = decode_device(p, d, d->d_stage + head, (int64_t)slot, (const int32_t*)d->d_stage, 0, 0, n, d->d_out, (int64_t)d->w * d->h, d->d_status, d->stream, launch);
+  if (rc != kOk) return rc;
+  if (hipMemcpyAsync(status, d->d_status, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream) != hipSuccess || hipStreamSynchronize(d->stream) != hipSuccess)
+    return fail(kErrHip, "%s_decode_host: the decode failed: %s", p.prefix, hipGetErrorString(hipGetLastError()));
+  return kOk;
+}
 
 }  // namespace
 #endif  // MDC_PNG_DECODE_KERNELS_H

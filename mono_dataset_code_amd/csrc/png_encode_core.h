@@ -8,7 +8,7 @@
 //   device                   the sample, filter and wave helpers of the filter kernels; Slot / slot_of; scan_units (the scan kernel's
 //                            clearing, wave scan and carry over a "bits of unit u" functor); pack_stored (the pack kernel's stored-block
 //                            gather); finish_files and crc_bytes (the bodies of the finish and crc kernels)
-//   host                     g_error / fail, DeviceGuard, crc32_host, put_be32, bound_of, grid_for, png_head, pack_parts, output_device
+//   host                     (codec_host.h: g_error / fail, DeviceGuard, resolve_device) crc32_host, put_be32, bound_of, grid_for, png_head, pack_parts, output_device
 // The filter kernel's 80-line body is not here: as a device function template it compiles to other registers than as the kernel itself
 // (79 instead of 69 VGPRs for the RGB pixel, past the 72 the tests allow), so each unit keeps its copy and the helpers are shared.
 // Nor are the pack kernel's header bits (pngw_pack_kernel came out one instruction longer with them here) and mdc_pngw.hip's
@@ -17,11 +17,11 @@
 #define MDC_PNG_ENCODE_CORE_H
 
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
+
+#include "codec_host.h"
 
 #define PNG_HD __host__ __device__ __forceinline__
 #include "png_block.h"
@@ -34,7 +34,6 @@ constexpr int kStreamAt = 43;        // signature 8, IHDR 25, length 4, "IDAT" 4
 constexpr int kRowsPerGroup = 16;
 constexpr int kMaxGrid = 8192;
 constexpr uint32_t kAdlerMod = 65521;
-constexpr int kErrArg = -1, kErrNoMem = -6;  // MDCP_ERR_ARG / MDCL_ERR_ARG, MDCP_ERR_NOMEM / MDCL_ERR_NOMEM
 
 // ---------------------------------------------------------------------------------------------------- pixels -> filtered bytes
 
@@ -190,30 +189,6 @@ __device__ __forceinline__ void crc_bytes(long long nimages, const uint32_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (dev < 0) return;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 uint32_t crc32_host(const uint8_t* p, size_t n) {
   uint32_t c = 0xFFFFFFFFu;

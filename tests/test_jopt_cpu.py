@@ -289,13 +289,16 @@ def test_product_build_identity_is_unchanged():
 
 
 def test_the_two_encoders_share_one_source():
-    """mdc_jenc.hip and mdc_jopt.hip include csrc/jpeg_encode_core.h, and neither defines what it holds"""
+    """mdc_jenc.hip and mdc_jopt.hip include csrc/jpeg_encode_core.h, and neither defines what it holds -- nor what that header takes
+    from csrc/codec_host.h, the one place of every codec library's error buffer and device guard"""
     from mono_dataset_code_amd import build
 
     core = open(build.JPEG_ENCODE_CORE).read()
+    shared = open(build.CODEC_HOST).read()
+    assert '#include "codec_host.h"' in core and "struct DeviceGuard" in shared and "struct DeviceGuard" not in core
     for src in (build.JENC_SOURCE, build.JOPT_SOURCE):
         text = open(src).read()
-        assert '#include "jpeg_encode_core.h"' in text
+        assert '#include "jpeg_encode_core.h"' in text and "struct DeviceGuard" not in text
         for name in ("void walk_block(", "struct BitPacker", "struct BitCounter", "void jenc_scan_kernel(", "void jenc_gather_kernel(", "void fdct_pass(",
-                     "kAcVals[162]", "struct DeviceGuard", "void huffman_table(", "long long blocks_of("):
+                     "kAcVals[162]", "void huffman_table(", "long long blocks_of(", "struct Encoder", "int64_t fetch(", "int output_device("):
             assert name in core and name not in text, (src, name)
