@@ -11,6 +11,7 @@
 #ifndef MDC_HOST_H
 #define MDC_HOST_H
 #include "mdc_hip.h"
+#include "mdc_lens.h" /* struct mdcn_model only: libmdc_host.so does not link libmdc_lens.so */
 
 #ifdef __cplusplus
 extern "C" {
@@ -32,7 +33,13 @@ MDC_API void mdch_fov_distort(mdch_fov*, float* x, float* y, int n);         /* 
 MDC_API void mdch_fov_undistort_f32(const mdch_fov*, const float* in, float* out, int n_in, int n_out); /* undistort<float> */
 MDC_API void mdch_fov_undistort_u8(const mdch_fov*, const unsigned char* in, float* out, int n_in, int n_out);
 
-MDC_API void mdch_fov_model(const mdch_fov*, mdc_fov_model* model);           /* lens model for mdc_distort_points_* */
+/* lens model for mdc_distort_points_*; all zeros for an object whose lens is not FOV (mdch_fov_lens_model: kind != 0) */
+MDC_API void mdch_fov_model(const mdch_fov*, mdc_fov_model* model);
+/* lensModel() -> *kind (0 FOV / pinhole, 1 RadTan, 2 EquiDistant alias KannalaBrandt), lensParameters() -> k[4]; returns isValid() */
+MDC_API int mdch_fov_lens_model(const mdch_fov*, int* kind, float k[4]);
+/* The object's cameras in pixels for the calls of include/mdc_lens.h (libmdc_lens.so): 1 for a valid RadTan / EquiDistant object and
+ * for a FOV object with omega 0 (kind MDCN_PINHOLE); 0, and a struct of zeros, for an invalid object or a FOV lens with omega != 0. */
+MDC_API int mdch_fov_mdcn_model(const mdch_fov*, mdcn_model* model);
 
 /* PhotometricUndistorter(std::string file, std::string vignetteImage, int w, int h) */
 MDC_API mdch_photo* mdch_photo_create(const char* pcalib_txt, const char* vignette_image, int w, int h);

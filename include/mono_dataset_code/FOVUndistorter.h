@@ -53,6 +53,16 @@ class MDC_API UndistorterFOV {
   const Eigen::Vector2i getOutputDims() const { return Eigen::Vector2i(out_w_, out_h_); }
   bool isValid() const { return valid_; }
 
+  // The lens model line 1 of camera.txt named: 0 = FOV / pinhole (a bare five-number line, `FOV ...`, `Pinhole ...`),
+  // 1 = RadTan (k1 k2 p1 p2), 2 = EquiDistant (k1 k2 k3 k4; `KannalaBrandt` is the same polynomial under DSO's other name).
+  // For 1 and 2 getOmega() is 0, getOriginalCalibration() / getK_org() give the input pinhole part as for FOV, and
+  // lensParameters() the four distortion coefficients (zeros for 0).  Neither is inline, and the class has no data member for
+  // them: its size and layout stay what they were before there were lens models (the members below), so a program compiled
+  // against an earlier version of this header -- which allocates that many bytes -- runs on this library unchanged.  What a RadTan / EquiDistant object holds beyond the members below lives in the library,
+  // keyed by the object (fov_undistorter.cpp: lens_states).
+  int lensModel() const;
+  const float* lensParameters() const;
+
  private:
   UndistorterFOV(const UndistorterFOV&);             // owning raw tables: not copyable
   UndistorterFOV& operator=(const UndistorterFOV&);
@@ -66,6 +76,8 @@ class MDC_API UndistorterFOV {
   float* remap_y_;
   bool valid_;
   mdc_ctx* gpu_;        // device context holding the uploaded remap (0 if no GPU)
+  // (no member may be added, removed or moved: see lensModel())
+  const float* lensCamera() const;  // kinds 1 and 2: fx fy cx cy of the input camera in pixels, as line 1 gave or implied them
 };
 
 // The task description calls this class "Undistorter"; the reference names it

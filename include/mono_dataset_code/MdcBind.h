@@ -18,5 +18,7 @@
 // status of mdc_set_photometric / mdc_set_remap.
 MDC_API int mdc_bind_objects(mdc_ctx* ctx, const UndistorterFOV* fov, const PhotometricUndistorter* photo);
 
-// The lens model of `fov` for mdc_distort_points_* (distortCoordinates on the GPU).
+// The lens model of `fov` for mdc_distort_points_* (distortCoordinates on the GPU).  An object whose lens is not FOV
+// (fov.lensModel() != 0: RadTan, EquiDistant) has none: *model is all zeros then (mdch_fov_mdcn_model, include/mdc_host.h, gives
+// its cameras for the calls of include/mdc_lens.h).
 MDC_API void mdc_fov_model_of(const UndistorterFOV& fov, mdc_fov_model* model);

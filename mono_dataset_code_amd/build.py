@@ -6,6 +6,7 @@
   the codec libraries, hipcc, gfx950    libmdc_jenc.so, libmdc_jopt.so, libmdc_zipw.so, libmdc_pngw.so, libmdc_pngw_rgb.so,
                                         libmdc_pnglz.so, libmdc_pngd.so, libmdc_pngdx.so: one translation unit each over shared core
                                         headers, all by one rule (_build_codec), outside libmdc_hip.so's build identity
+  libmdc_lens.so, hipcc, gfx950         the RadTan / EquiDistant / pinhole lens models (include/mdc_lens.h), by the same rule
   bin/                                  the programs; tests/native/ programs are built into a place the tests name
 
 All land next to this file so they travel with the source tree to the GPU box.
@@ -39,7 +40,8 @@ HOST_DEPS = HOST_SOURCES + [os.path.join(HOST, "mdc_host_exports.map"), os.path.
                             os.path.join(HOST, "frame_source.h"), os.path.join(HOST, "decode_pool.h"), os.path.join(HOST, "prefetch_cache.h"),
                             os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"), os.path.join(CSRC, "png_inflate_core.h"),
                             os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h"),
-                            os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_host.h"),
+                            os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_host.h"), os.path.join(INC, "mdc_lens.h"),
+                            os.path.join(CSRC, "lens_point_model.h"), os.path.join(CSRC, "fov_point_model.h"),
                             os.path.join(INC, "mono_dataset_code", "FOVUndistorter.h"),
                             os.path.join(INC, "mono_dataset_code", "PhotometricUndistorter.h"),
                             os.path.join(INC, "mono_dataset_code", "ExposureImage.h"),
@@ -257,23 +259,24 @@ def build_bench(force=False):
 CODEC_HOST = os.path.join(CSRC, "codec_host.h")  # what every codec library's host side has: the last error, the device guard, device resolution
 
 
-def _build_codec(out, source, deps, export_map, zipw=False, defines=(), force=False):
+def _build_codec(out, source, deps, export_map, zipw=False, defines=(), force=False, extra_flags=()):
     """One codec library: a single translation unit (`source` and the headers in `deps`), a library of its own outside
-    libmdc_hip.so's build identity.  zipw: it stands on libmdc_zipw.so, which is built first and linked."""
+    libmdc_hip.so's build identity.  zipw: it stands on libmdc_zipw.so, which is built first and linked.  extra_flags: compiler
+    flags beyond the common ones (libmdc_lens.so's floating-point rules)."""
     if zipw:
         build_zipw(force)
     if force or _stale(out, [source, CODEC_HOST] + deps + [export_map] + ([LIB_ZIPW] if zipw else [])):
         _run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall"] +
-             ["-D" + d for d in defines] + ["-I" + INC, source] + (["-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN"] if zipw else []) +
+             list(extra_flags) + ["-D" + d for d in defines] + ["-I" + INC, source] + (["-L" + PKG, "-lmdc_zipw", "-Wl,-rpath,$ORIGIN"] if zipw else []) +
              ["-Wl,--version-script=" + export_map, "-o", out])
     return out
 
 
-def _build_native_program(source, out, sanitize=True):
+def _build_native_program(source, out, sanitize=True, flags=()):
     """A stand-alone test program of tests/native/ (its own main, pure host code over a header of csrc/), under AddressSanitizer and
     UndefinedBehaviorSanitizer."""
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
-    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", source), "-o", out])
+    _run(["g++", "-O1", "-g", "-std=c++11", "-Wall", "-Werror"] + list(flags) + san + ["-I" + CSRC, os.path.join(ROOT, "tests", "native", source), "-o", out])
     return out
 
 
@@ -404,6 +407,27 @@ def build_pngdx_core_program(out, sanitize=True):
     return _build_native_program("pngdx_core.cpp", out, sanitize)
 
 
+LIB_LENS = os.path.join(PKG, "libmdc_lens.so")
+LENS_SOURCE = os.path.join(CSRC, "mdc_lens.hip")
+LENS_MODEL = os.path.join(CSRC, "lens_point_model.h")  # the lens arithmetic and the crop rule: libmdc_lens.so, libmdc_host.so and a CPU test program
+FOV_MODEL = os.path.join(CSRC, "fov_point_model.h")  # atanf_host_libm (read here, never edited: it is part of libmdc_hip.so's identity)
+LENS_EXPORT_MAP = os.path.join(CSRC, "mdc_lens_exports.map")
+LENS_FP_FLAGS = ["-ffp-contract=off", "-fno-fast-math"]  # IEEE single precision, no FMA: the device gives the host's bits
+
+
+def build_lens(force=False):
+    """libmdc_lens.so: the pinhole / RadTan / EquiDistant lens models on the device (include/mdc_lens.h) -- one translation unit over
+    the header it shares with libmdc_host.so and the CPU test program; it links nothing of this project, and it is outside
+    libmdc_hip.so's build identity.  libmdc_host.so loads it at run time for bulk distortCoordinates() calls, nothing links it."""
+    return _build_codec(LIB_LENS, LENS_SOURCE, [LENS_MODEL, FOV_MODEL, os.path.join(INC, "mdc_lens.h")], LENS_EXPORT_MAP, force=force, extra_flags=LENS_FP_FLAGS)
+
+
+def build_lens_core_program(out, sanitize=True):
+    """tests/native/lens_core.cpp: lens_point_model.h (the lens arithmetic, the crop rule, the border rules) as a stand-alone program
+    (its own main), under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_lens_cpu.py).  Pure host code."""
+    return _build_native_program("lens_core.cpp", out, sanitize, flags=LENS_FP_FLAGS)
+
+
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")
 MULTI_SOURCE = os.path.join(CSRC, "mdc_multi.hip")
 
@@ -481,6 +505,7 @@ def build_all(force=False):
     build_pnglz(force)
     build_pngd(force)
     build_pngdx(force)
+    build_lens(force)
     build_debug()
     build_fault_injection()
     return LIB_HIP, LIB_HOST, LIB_MULTI

@@ -78,6 +78,29 @@ class FovModel(C.Structure):
                 ("out_w", C.c_int), ("out_h", C.c_int)]
 
 
+LENS_PINHOLE, LENS_RADTAN, LENS_EQUIDISTANT = 0, 1, 2  # MDCN_PINHOLE, MDCN_RADTAN, MDCN_EQUIDISTANT
+LENS_NAMES = {0: "FOV / pinhole", 1: "RadTan", 2: "EquiDistant"}  # UndistorterFOV.lens_model()
+
+
+class LensModel(C.Structure):
+    """include/mdc_lens.h: mdcn_model -- a raw camera (pinhole, RadTan or EquiDistant) and the rectified pinhole, in pixels."""
+    _fields_ = [("kind", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k", C.c_float * 4),
+                ("in_w", C.c_int), ("in_h", C.c_int), ("ofx", C.c_float), ("ofy", C.c_float), ("ocx", C.c_float), ("ocy", C.c_float),
+                ("out_w", C.c_int), ("out_h", C.c_int)]
+
+    @classmethod
+    def make(cls, kind, cam, rect, in_size=(0, 0), out_size=(0, 0)):
+        """cam = fx fy cx cy k0 k1 k2 k3, rect = ofx ofy ocx ocy"""
+        m = cls()
+        m.kind = int(kind)
+        m.fx, m.fy, m.cx, m.cy = (float(v) for v in cam[:4])
+        for i in range(4):
+            m.k[i] = float(cam[4 + i])
+        m.ofx, m.ofy, m.ocx, m.ocy = (float(v) for v in rect)
+        (m.in_w, m.in_h), (m.out_w, m.out_h) = in_size, out_size
+        return m
+
+
 class MdcInfo(C.Structure):
     _fields_ = [("device", C.c_int), ("in_w", C.c_int), ("in_h", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int),
                 ("valid_gamma", C.c_int), ("valid_vignette", C.c_int), ("valid_remap", C.c_int), ("tiled", C.c_int),
@@ -223,6 +246,8 @@ HOST_API = {  # include/mdc_host.h (libmdc_host.so)
     "mdch_fov_undistort_f32": (None, [_vp, _vp, _vp, _i, _i]),
     "mdch_fov_undistort_u8": (None, [_vp, _vp, _vp, _i, _i]),
     "mdch_fov_model": (None, [_vp, _P(FovModel)]),
+    "mdch_fov_lens_model": (_i, [_vp, _P(_i), _P(_f)]),
+    "mdch_fov_mdcn_model": (_i, [_vp, _P(LensModel)]),
     # ---- class PhotometricUndistorter
     "mdch_photo_create": (_vp, [_cp, _cp, _i, _i]),
     "mdch_photo_destroy": (None, [_vp]),
@@ -372,6 +397,12 @@ PNGDX_API = {  # include/mdc_pngdx.h (libmdc_pngdx.so: the device PNG decoder wi
     "mdcx_stream": (_vp, [_vp]),
     "mdcx_synchronize": (_i, [_vp]),
 }
+LENS_API = {  # include/mdc_lens.h (libmdc_lens.so: the pinhole / RadTan / EquiDistant lens models on the device, a library of its own)
+    "mdcn_last_error": (_cp, []),
+    "mdcn_distort_points_device": (_i, [_P(LensModel), _vp, _vp, _i64, _vp]),
+    "mdcn_distort_points_host": (_i, [_i, _P(LensModel), _vp, _vp, _i64]),
+    "mdcn_remap_device": (_i, [_P(LensModel), _vp, _vp, _vp, _vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
@@ -383,6 +414,7 @@ LIB_PNGW_RGB_PATH = os.path.join(_PKG, "libmdc_pngw_rgb.so")
 LIB_PNGLZ_PATH = os.path.join(_PKG, "libmdc_pnglz.so")
 LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
 LIB_PNGDX_PATH = os.path.join(_PKG, "libmdc_pngdx.so")
+LIB_LENS_PATH = os.path.join(_PKG, "libmdc_lens.so")
 _hip = None
 _host = None
 
@@ -447,6 +479,7 @@ pnglz_lib = _lazy_lib(LIB_PNGLZ_PATH, PNGLZ_API,
                       "libmdc_pnglz.so: the PNG encoder with LZ77 matches for device-resident gray and RGB images (include/mdc_pnglz.h).")
 pngd_lib = _lazy_lib(LIB_PNGD_PATH, PNGD_API, "libmdc_pngd.so: the PNG decoder for frames whose zlib streams are in device or host memory (include/mdc_pngd.h).")
 pngdx_lib = _lazy_lib(LIB_PNGDX_PATH, PNGDX_API, "libmdc_pngdx.so: the PNG decoder with a parallel inflate for streams with matches (include/mdc_pngdx.h).")
+lens_lib = _lazy_lib(LIB_LENS_PATH, LENS_API, "libmdc_lens.so: the pinhole / RadTan / EquiDistant lens models on the device (include/mdc_lens.h).")
 
 
 def hip_lib():
@@ -1094,8 +1127,24 @@ class UndistorterFOV:
         return rx, ry
 
     def model(self):
+        """the FOV model for Context.distort_points_*; raises for a RadTan / EquiDistant camera (the C call gives zeros there)"""
+        if self.lens_model()[0] != 0:
+            raise MdcError(ERR_ARG, "the camera's lens is %s, which has no FOV model: use mdcn_model()" % LENS_NAMES.get(self.lens_model()[0]))
         m = FovModel()
         self._L.mdch_fov_model(self._h, C.byref(m))
+        return m
+
+    def lens_model(self):
+        """-> (lensModel(): 0 FOV / pinhole, 1 RadTan, 2 EquiDistant; lensParameters() as 4 floats)"""
+        kind, k = _i(0), (_f * 4)()
+        self._L.mdch_fov_lens_model(self._h, C.byref(kind), k)
+        return kind.value, np.array(k[:], np.float32)
+
+    def mdcn_model(self):
+        """the cameras in pixels as a LensModel for capi.Lens; raises where there is none (invalid object, FOV lens with omega != 0)"""
+        m = LensModel()
+        if not self._L.mdch_fov_mdcn_model(self._h, C.byref(m)):
+            raise MdcError(ERR_ARG, "no mdcn_model for this object (invalid, or a FOV lens with omega != 0)")
         return m
 
     def distort_coordinates(self, x, y):
@@ -1393,6 +1442,32 @@ class PngDecoder:
         d_frames = _vp()
         self._check(self._fn("decode_host")(self._h, ptrs, _np_ptr(sizes) if n else None, n, _np_ptr(status), C.byref(d_frames)))
         return status[:n], d_frames.value
+
+
+class Lens:
+    """The calls of include/mdc_lens.h on one LensModel (UndistorterFOV.mdcn_model(), or LensModel.make)."""
+
+    def __init__(self, model):
+        self._L = lens_lib()
+        self.model = model
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MdcError(int(rc), self._L.mdcn_last_error().decode())
+        return rc
+
+    def distort_points_device(self, d_x, d_y, n, stream=0):
+        """n points in the device arrays at d_x, d_y, in place; enqueues on `stream` and does not synchronise"""
+        self._check(self._L.mdcn_distort_points_device(C.byref(self.model), d_x, d_y, int(n), _stream(stream)))
+
+    def distort_points_host(self, x, y, device=-1):
+        """float32 arrays, in place, blocking; untouched when the call fails (it raises)"""
+        assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size and x.flags.c_contiguous and y.flags.c_contiguous
+        self._check(self._L.mdcn_distort_points_host(int(device), C.byref(self.model), _np_ptr(x), _np_ptr(y), x.size))
+
+    def remap_device(self, d_rx, d_ry, d_black, stream=0):
+        """the model's out_w x out_h remap tables into device arrays, *d_black (an int32 on the device) = 1 if any entry is black"""
+        self._check(self._L.mdcn_remap_device(C.byref(self.model), d_rx, d_ry, d_black, _stream(stream)))
 
 
 def huffman_lengths_device(d_hist, nsym, limit, d_lengths, stream=None):

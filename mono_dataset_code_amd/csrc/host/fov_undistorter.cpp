@@ -11,15 +11,21 @@
 // gfx950 kernel behind mdc_undistort_host_* (include/mdc_hip.h).
 #include "FOVUndistorter.h"
 
+#include <dlfcn.h>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <map>
+#include <mutex>
 #include <string>
 
 #include "mdc_hip.h"
+#include "mdc_lens.h"
 #include "host_device.h"
 #include "../fov_point_model.h"  // atanf_host_libm: the restatement the device runs, checked against THIS process's libm below
+#include "../lens_point_model.h"  // the RadTan / EquiDistant arithmetic and the crop rule, shared with libmdc_lens.so's kernels
 
 namespace {
 
@@ -31,25 +37,105 @@ struct CameraFile {
   float out[5];  // only for kExplicit
   int out_w, out_h;
 };
+// What line 1 adds when it names RadTan, EquiDistant or KannalaBrandt (kind 0: it did not).
+struct LensLine {
+  int kind;
+  std::string name;  // the keyword as written
+  float k[4];
+  float cam[4];  // fx fy cx cy in pixels
+};
 enum { kExplicit = 0, kCrop = -1, kFull = -2 };
 enum ParseResult { kParsed, kUnreadable, kBadHeader, kNoRectification, kBadOutputPars, kBadOutputSize };
 
-ParseResult parse_camera_file(const char* path, CameraFile& c) {
+// Line 1 in DSO's keyword grammar (the same authors' later reader of the same folder layout):
+//   FOV fx fy cx cy omega | Pinhole fx fy cx cy 0 | RadTan fx fy cx cy k1 k2 p1 p2 | EquiDistant fx fy cx cy k1 k2 k3 k4 |
+//   KannalaBrandt fx fy cx cy k1 k2 k3 k4
+// Units, DSO's rule: cx < 1 && cy < 1 means the four intrinsics are relative to the input size, else they are pixels.  A wrong
+// parameter count, a value that is not finite, fx <= 0 or fy <= 0 is a bad header.  FOV / Pinhole end as the bare line's five
+// relative numbers in c.in (pixels become relative first, in float), so the object is the bare line's; the new kinds keep their
+// pixel intrinsics in c.cam (pixels as they stand; relative ones as fx*w, fy*h, cx*w - 0.5, cy*h - 0.5, the subtraction in double and
+// narrowed, as InputModel does) and the relative ones in c.in with c.in[4] = 0.
+enum KeywordResult { kNoKeyword, kKeywordBad, kKeywordFov, kKeywordLens };
+
+KeywordResult parse_keyword_line(const std::string& line1, const std::string& line2, CameraFile& c, LensLine& lens) {
+  size_t at = line1.find_first_not_of(" \t");
+  if (at == std::string::npos || !std::isalpha((unsigned char)line1[at])) return kNoKeyword;
+  const size_t end = line1.find_first_of(" \t", at);
+  const std::string word = line1.substr(at, end == std::string::npos ? std::string::npos : end - at);
+  int kind, want;
+  if (word == "FOV" || word == "Pinhole") kind = mdc::LENS_PINHOLE, want = 5;  // the existing path (omega 0 is its pinhole case)
+  else if (word == "RadTan") kind = mdc::LENS_RADTAN, want = 8;
+  else if (word == "EquiDistant" || word == "KannalaBrandt") kind = mdc::LENS_EQUIDISTANT, want = 8;
+  else return kKeywordBad;
+  float v[9];
+  int n = 0;
+  const char* p = end == std::string::npos ? "" : line1.c_str() + end;
+  for (;;) {
+    while (*p == ' ' || *p == '\t' || *p == '\r') p++;
+    if (!*p) break;
+    char* q;
+    const float x = std::strtof(p, &q);
+    if (q == p || n == 9 || !std::isfinite(x)) return kKeywordBad;
+    v[n++] = x;
+    p = q;
+  }
+  if (n != want || !(v[0] > 0) || !(v[1] > 0)) return kKeywordBad;
+  if (std::sscanf(line2.c_str(), "%d %d", &c.in_w, &c.in_h) != 2) return kKeywordBad;
+  const bool relative = v[2] < 1 && v[3] < 1;
+  const int w = c.in_w, h = c.in_h;
+  if (relative) {
+    for (int i = 0; i < 4; i++) c.in[i] = v[i];
+  } else {
+    c.in[0] = v[0] / w;
+    c.in[1] = v[1] / h;
+    c.in[2] = (v[2] + 0.5f) / w;
+    c.in[3] = (v[3] + 0.5f) / h;
+  }
+  if (kind == mdc::LENS_PINHOLE) {
+    c.in[4] = v[4];
+    return kKeywordFov;
+  }
+  c.in[4] = 0;
+  lens.kind = kind;
+  lens.name = word;
+  for (int i = 0; i < 4; i++) lens.k[i] = v[4 + i];
+  if (relative) {
+    lens.cam[0] = v[0] * w;
+    lens.cam[1] = v[1] * h;
+    lens.cam[2] = v[2] * w - 0.5;  // double subtraction, narrowed
+    lens.cam[3] = v[3] * h - 0.5;
+  } else {
+    for (int i = 0; i < 4; i++) lens.cam[i] = v[i];
+  }
+  return kKeywordLens;
+}
+
+ParseResult parse_camera_file(const char* path, CameraFile& c, LensLine& lens) {
   std::ifstream f(path);
   if (!f.good()) return kUnreadable;
   std::string line[4];
   for (int i = 0; i < 4; i++) std::getline(f, line[i]);
 
-  const bool head = std::sscanf(line[0].c_str(), "%f %f %f %f %f", &c.in[0], &c.in[1], &c.in[2], &c.in[3], &c.in[4]) == 5 &&
-                    std::sscanf(line[1].c_str(), "%d %d", &c.in_w, &c.in_h) == 2;
+  const KeywordResult kw = parse_keyword_line(line[0], line[1], c, lens);
+  if (kw == kKeywordBad) return kBadHeader;
+  const bool head = kw != kNoKeyword ||
+                    (std::sscanf(line[0].c_str(), "%f %f %f %f %f", &c.in[0], &c.in[1], &c.in[2], &c.in[3], &c.in[4]) == 5 &&
+                     std::sscanf(line[1].c_str(), "%d %d", &c.in_w, &c.in_h) == 2);
   if (!head) return kBadHeader;
   std::printf("Input resolution: %d %d\n", c.in_w, c.in_h);
-  std::printf("Input Calibration (fx fy cx cy): %f %f %f %f %f\n", c.in_w * c.in[0], c.in_h * c.in[1], c.in_w * c.in[2],
-              c.in_h * c.in[3], c.in[4]);
+  if (kw == kKeywordLens)
+    std::printf("Input Calibration (%s fx fy cx cy k): %f %f %f %f %f %f %f %f\n", lens.name.c_str(), lens.cam[0], lens.cam[1], lens.cam[2],
+                lens.cam[3], lens.k[0], lens.k[1], lens.k[2], lens.k[3]);
+  else
+    std::printf("Input Calibration (fx fy cx cy): %f %f %f %f %f\n", c.in_w * c.in[0], c.in_h * c.in[1], c.in_w * c.in[2],
+                c.in_h * c.in[3], c.in[4]);
 
   if (line[2] == "crop") {
     c.mode = kCrop;
     std::printf("Out: Crop\n");
+  } else if (line[2] == "full" && kw == kKeywordLens) {
+    std::printf("Out: Full is not implemented for this lens model... not rectifying.\n");
+    return kBadOutputPars;
   } else if (line[2] == "full") {
     c.mode = kFull;
     std::printf("Out: Full\n");
@@ -161,6 +247,123 @@ void warp_points(const float calib_in[5], int in_w, int in_h, const float calib_
   }
 }
 
+// ---- RadTan / EquiDistant (csrc/lens_point_model.h holds the arithmetic) ----------------------------------------------
+
+mdc::LensModel lens_model_of(const float cam[4], const float k[4], const float calib_out[5], int out_w, int out_h) {
+  mdc::LensModel m;
+  m.fx = cam[0];
+  m.fy = cam[1];
+  m.cx = cam[2];
+  m.cy = cam[3];
+  for (int i = 0; i < 4; i++) m.k[i] = k[i];
+  mdc::lens_set_rectified(m, calib_out, out_w, out_h);  // pixel units derived from the stored normalised values, by every consumer alike
+  return m;
+}
+
+// Rectified intrinsics of a RadTan / EquiDistant camera, normalised as pick_output_intrinsics normalises them: `crop` by DSO's search,
+// else the explicit relative line 3.  false (after a message): the object stays invalid.
+bool pick_output_intrinsics_lens(const CameraFile& c, const LensLine& lens, float norm[5]) {
+  float ofx, ofy, ocx, ocy;
+  if (c.mode == kCrop) {
+    mdc::LensModel m = mdc::LensModel();
+    for (int i = 0; i < 4; i++) m.k[i] = lens.k[i];
+    m.fx = lens.cam[0];
+    m.fy = lens.cam[1];
+    m.cx = lens.cam[2];
+    m.cy = lens.cam[3];
+    mdc::LensCrop crop;
+    const int rc = mdc::lens_crop(lens.kind, m, c.in_w, c.in_h, c.out_w, c.out_h, &crop);
+    if (rc != mdc::LENS_CROP_OK) {
+      std::printf(rc == mdc::LENS_CROP_SIZE ? "Out: Crop needs an output of at least 2 x 2 pixels... not rectifying.\n"
+                  : rc == mdc::LENS_CROP_NOTHING_INSIDE ? "Out: Crop found no point of the lens model inside the input image... not rectifying.\n"
+                                                        : "Out: Crop did not converge in 500 rounds... not rectifying.\n");
+      return false;
+    }
+    ofx = crop.ofx;
+    ofy = crop.ofy;
+    ocx = crop.ocx;
+    ocy = crop.ocy;
+    std::printf("crop rounds: %d\n", crop.rounds);
+    std::printf("new K: %f %f %f %f\n", ofx, ofy, ocx, ocy);
+    std::printf("old K: %f %f %f %f\n", m.fx, m.fy, m.cx, m.cy);
+  } else {
+    ofx = c.out[0] * c.out_w;
+    ofy = c.out[1] * c.out_h;
+    ocx = c.out[2] * c.out_w - 0.5;
+    ocy = c.out[3] * c.out_h - 0.5;
+  }
+  norm[0] = ofx / c.out_w;
+  norm[1] = ofy / c.out_h;
+  norm[2] = (ocx + 0.5) / c.out_w;
+  norm[3] = (ocy + 0.5) / c.out_h;
+  norm[4] = 0;
+  return true;
+}
+
+void warp_points_lens(int kind, const mdc::LensModel& m, float* xs, float* ys, long n) {
+  if (kind == mdc::LENS_RADTAN)
+    for (long i = 0; i < n; i++) mdc::lens_distort_point<mdc::LENS_RADTAN>(m, xs[i], ys[i]);
+  else
+    for (long i = 0; i < n; i++) mdc::lens_distort_point<mdc::LENS_EQUIDISTANT>(m, xs[i], ys[i]);
+}
+
+// libmdc_lens.so's bulk call, loaded at run time the way device_lanes.cpp loads the PNG decoders: the file next to this library
+// (or the one MDC_LIB_LENS names), opened once per process and never closed (it holds a HIP module); 0 when it is not there.
+typedef int (*LensDistortHost)(int, const mdcn_model*, float*, float*, int64_t);
+struct LensApi {
+  LensDistortHost distort_points_host;
+  const char* (*last_error)();
+};
+
+const LensApi* load_lens_api() {
+  std::string path;
+  if (const char* e = std::getenv("MDC_LIB_LENS")) {
+    path = e;
+  } else {
+    Dl_info info;
+    if (dladdr((void*)&mdc_host::open_device_context, &info) && info.dli_fname) {
+      path = info.dli_fname;
+      const size_t sl = path.rfind('/');
+      path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
+    }
+    path += "libmdc_lens.so";
+  }
+  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);
+  if (!lib) return 0;
+  static LensApi api;
+  api.distort_points_host = (LensDistortHost)dlsym(lib, "mdcn_distort_points_host");
+  api.last_error = (const char* (*)())dlsym(lib, "mdcn_last_error");
+  return api.distort_points_host && api.last_error ? &api : 0;
+}
+
+const LensApi* lens_api() {
+  static const LensApi* api = load_lens_api();
+  return api;
+}
+
+// The device's atanf is a restatement of ONE libm's algorithm (glibc's fdlibm atanf).  A process linked against another libm
+// -- a newer glibc whose atanf is correctly rounded, musl, a vendor libm -- would get last-bit differences between small
+// calls (host loop, ::atanf) and large ones (device): checked once against the libm this process really runs, on a spread of
+// arguments through every interval of the algorithm; on any difference bulk calls stay on the host, like the small ones.
+// (EquiDistant's host loop runs the restatement itself, so its bits are the device's whatever the libm; the check guards its bulk
+// path all the same, so that one rule decides for every lens with an atanf in it.)
+bool libm_is_the_restated_one() {
+  static const bool same = [] {
+    uint32_t bad = 0;
+    for (uint32_t u = 0x30000000u; u < 0x4d800000u && !bad; u += 9973u) {  // 2^-31 .. 2^28, ~49,000 arguments, both signs
+      const float x = mdc::fov_float(u);
+      if (mdc::fov_bits(mdc::atanf_host_libm(x)) != mdc::fov_bits(::atanf(x)) ||
+          mdc::fov_bits(mdc::atanf_host_libm(-x)) != mdc::fov_bits(::atanf(-x)))
+        bad = u;
+    }
+    if (bad)
+      std::fprintf(stderr, "UndistorterFOV: this process's atanf differs from the algorithm the GPU kernel restates (first at %a): "
+                           "distortCoordinates stays on the host for every point count\n", mdc::fov_float(bad));
+    return bad == 0;
+  }();
+  return same;
+}
+
 void set_pinhole(Eigen::Matrix3f& k, const float rel[5], int w, int h) {
   k.setIdentity();
   k(0, 0) = rel[0] * w;
@@ -169,19 +372,73 @@ void set_pinhole(Eigen::Matrix3f& k, const float rel[5], int w, int h) {
   k(1, 2) = rel[3] * h - 0.5;
 }
 
+// What a RadTan / EquiDistant object holds beyond the class's members.  The class keeps the size and layout it had before (a program
+// compiled against an earlier header allocates exactly that many bytes), so this lives here, keyed by the object: made by its constructor,
+// dropped by its destructor, and read through pointers that stay put for the object's life (map nodes do not move).  FOV objects
+// have no entry.  The table itself is never destroyed: objects with static storage may outlive this file's statics.
+struct LensState {
+  int kind;
+  float k[4];
+  float cam[4];  // fx fy cx cy in pixels
+};
+std::mutex& lens_mutex() {
+  static std::mutex* m = new std::mutex;
+  return *m;
+}
+std::map<const UndistorterFOV*, LensState>& lens_states() {
+  static std::map<const UndistorterFOV*, LensState>* t = new std::map<const UndistorterFOV*, LensState>;
+  return *t;
+}
+const LensState* find_lens_state(const UndistorterFOV* u) {
+  std::lock_guard<std::mutex> lock(lens_mutex());
+  const std::map<const UndistorterFOV*, LensState>::const_iterator it = lens_states().find(u);
+  return it == lens_states().end() ? 0 : &it->second;
+}
+void keep_lens_state(const UndistorterFOV* u, const LensLine& lens) {
+  LensState s;
+  s.kind = lens.kind;
+  for (int i = 0; i < 4; i++) {
+    s.k[i] = lens.k[i];
+    s.cam[i] = lens.cam[i];
+  }
+  std::lock_guard<std::mutex> lock(lens_mutex());
+  lens_states()[u] = s;
+}
+void drop_lens_state(const UndistorterFOV* u) {
+  std::lock_guard<std::mutex> lock(lens_mutex());
+  lens_states().erase(u);
+}
+const float kNoLensParameters[4] = {0, 0, 0, 0};
+
 }  // namespace
+
+int UndistorterFOV::lensModel() const {
+  const LensState* s = find_lens_state(this);
+  return s ? s->kind : 0;
+}
+const float* UndistorterFOV::lensParameters() const {
+  const LensState* s = find_lens_state(this);
+  return s ? s->k : kNoLensParameters;
+}
+const float* UndistorterFOV::lensCamera() const {
+  const LensState* s = find_lens_state(this);
+  return s ? s->cam : kNoLensParameters;
+}
 
 UndistorterFOV::UndistorterFOV()
     : in_w_(0), in_h_(0), out_w_(0), out_h_(0), remap_x_(0), remap_y_(0), valid_(false), gpu_(0) {
   for (int i = 0; i < 5; i++) calib_in_[i] = calib_out_[i] = 0;
+  drop_lens_state(this);  // (memory that held an object which was never destroyed)
 }
 
 UndistorterFOV::UndistorterFOV(const char* configFileName)
     : in_w_(0), in_h_(0), out_w_(0), out_h_(0), remap_x_(0), remap_y_(0), valid_(false), gpu_(0) {
   for (int i = 0; i < 5; i++) calib_in_[i] = calib_out_[i] = 0;
+  drop_lens_state(this);  // (memory that held an object which was never destroyed)
 
   CameraFile cam = CameraFile();
-  const ParseResult pr = parse_camera_file(configFileName, cam);
+  LensLine lens = LensLine();
+  const ParseResult pr = parse_camera_file(configFileName, cam, lens);
   if (pr == kUnreadable || pr == kBadHeader) {
     std::printf("Failed to read camera calibration (invalid format?)\nCalibration file: %s\n", configFileName);
     return;
@@ -192,12 +449,17 @@ UndistorterFOV::UndistorterFOV(const char* configFileName)
   for (int i = 0; i < 5; i++) calib_in_[i] = cam.in[i];
   in_w_ = cam.in_w;
   in_h_ = cam.in_h;
+  if (lens.kind != 0) keep_lens_state(this, lens);
   if (pr != kParsed) return;
+  if (lens.kind != 0 && !pick_output_intrinsics_lens(cam, lens, calib_out_)) {
+    for (int i = 0; i < 5; i++) calib_out_[i] = 0;
+    return;
+  }
   out_w_ = cam.out_w;
   out_h_ = cam.out_h;
   valid_ = true;
 
-  pick_output_intrinsics(cam, calib_out_);
+  if (lens.kind == 0) pick_output_intrinsics(cam, calib_out_);
 
   // identity grid pushed through the lens model (:223-232)
   const int n = out_w_ * out_h_;
@@ -208,7 +470,8 @@ UndistorterFOV::UndistorterFOV(const char* configFileName)
       remap_x_[x + y * out_w_] = x;
       remap_y_[x + y * out_w_] = y;
     }
-  warp_points(calib_in_, in_w_, in_h_, calib_out_, out_w_, out_h_, remap_x_, remap_y_, n);
+  if (lens.kind == 0) warp_points(calib_in_, in_w_, in_h_, calib_out_, out_w_, out_h_, remap_x_, remap_y_, n);
+  else warp_points_lens(lens.kind, lens_model_of(lens.cam, lens.k, calib_out_, out_w_, out_h_), remap_x_, remap_y_, n);
 
   // border rules (:235-251): exact hits on the first/last row or column are
   // nudged inside; everything not strictly inside becomes the black sentinel.
@@ -241,6 +504,7 @@ UndistorterFOV::UndistorterFOV(const char* configFileName)
 }
 
 UndistorterFOV::~UndistorterFOV() {
+  drop_lens_state(this);
   if (gpu_) mdc_destroy(gpu_);
   delete[] remap_x_;
   delete[] remap_y_;
@@ -260,24 +524,35 @@ void UndistorterFOV::distortCoordinates(float* in_x, float* in_y, int n) {
     const char* e = std::getenv("MDC_DISTORT_GPU_MIN");
     return e ? std::atol(e) : 65536l;
   }();
-  // The device's atanf is a restatement of ONE libm's algorithm (glibc's fdlibm atanf).  A process linked against another libm
-  // -- a newer glibc whose atanf is correctly rounded, musl, a vendor libm -- would get last-bit differences between small
-  // calls (host loop, ::atanf) and large ones (device): checked once against the libm this process really runs, on a spread of
-  // arguments through every interval of the algorithm; on any difference bulk calls stay on the host, like the small ones.
-  static const bool libm_is_the_restated_one = [] {
-    uint32_t bad = 0;
-    for (uint32_t u = 0x30000000u; u < 0x4d800000u && !bad; u += 9973u) {  // 2^-31 .. 2^28, ~49,000 arguments, both signs
-      const float x = mdc::fov_float(u);
-      if (mdc::fov_bits(mdc::atanf_host_libm(x)) != mdc::fov_bits(::atanf(x)) ||
-          mdc::fov_bits(mdc::atanf_host_libm(-x)) != mdc::fov_bits(::atanf(-x)))
-        bad = u;
+  const LensState* const ls = find_lens_state(this);
+  if (ls) {
+    // RadTan / EquiDistant: the same threshold; the bulk call is libmdc_lens.so's, loaded at run time.  Where the library or the GPU
+    // is missing the host loop does the work and says so once -- the bits are the same either way (one header, no FMA on either side).
+    const mdc::LensModel lm = lens_model_of(ls->cam, ls->k, calib_out_, out_w_, out_h_);
+    if (gpu_min > 0 && n >= gpu_min && (ls->kind != mdc::LENS_EQUIDISTANT || libm_is_the_restated_one())) {
+      const LensApi* api = lens_api();
+      mdc_info info;
+      if (api && gpu_ && mdc_get_info(gpu_, &info) == MDC_OK) {
+        mdcn_model m;
+        m.kind = ls->kind;
+        m.fx = lm.fx, m.fy = lm.fy, m.cx = lm.cx, m.cy = lm.cy;
+        for (int i = 0; i < 4; i++) m.k[i] = lm.k[i];
+        m.in_w = in_w_, m.in_h = in_h_;
+        m.ofx = lm.ofx, m.ofy = lm.ofy, m.ocx = lm.ocx, m.ocy = lm.ocy;
+        m.out_w = out_w_, m.out_h = out_h_;
+        if (api->distort_points_host(info.device, &m, in_x, in_y, n) == MDCN_OK) return;
+        std::fprintf(stderr, "UndistorterFOV::distortCoordinates: the GPU call failed (%s); computing %d points on the host\n", api->last_error(), n);
+      } else {
+        static bool said = false;
+        if (!said) std::fprintf(stderr, "UndistorterFOV::distortCoordinates: %s; bulk calls are computed on the host (same results)\n",
+                                api ? "no GPU context" : "libmdc_lens.so could not be loaded (MDC_LIB_LENS names another file)");
+        said = true;
+      }
     }
-    if (bad)
-      std::fprintf(stderr, "UndistorterFOV: this process's atanf differs from the algorithm the GPU kernel restates (first at %a): "
-                           "distortCoordinates stays on the host for every point count\n", mdc::fov_float(bad));
-    return bad == 0;
-  }();
-  if (gpu_ && gpu_min > 0 && n >= gpu_min && libm_is_the_restated_one) {
+    warp_points_lens(ls->kind, lm, in_x, in_y, n);
+    return;
+  }
+  if (gpu_ && gpu_min > 0 && n >= gpu_min && libm_is_the_restated_one()) {
     mdc_fov_model m;
     for (int i = 0; i < 5; i++) {
       m.in_calib[i] = calib_in_[i];

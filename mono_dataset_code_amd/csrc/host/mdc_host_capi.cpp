@@ -21,6 +21,7 @@ struct MdcHostAccess {
   static const float* ry(const UndistorterFOV& u) { return u.remap_y_; }
   static const float* calib_out(const UndistorterFOV& u) { return u.calib_out_; }
   static const float* calib_in(const UndistorterFOV& u) { return u.calib_in_; }
+  static const float* lens_cam(const UndistorterFOV& u) { return u.lensCamera(); }
   static bool has_gpu(const UndistorterFOV& u) { return u.gpu_ != 0; }
   static bool has_gpu(const PhotometricUndistorter& p) { return p.gpu_ != 0; }
   static bool valid_gamma(const PhotometricUndistorter& p) { return p.valid_gamma_; }
@@ -53,6 +54,10 @@ int mdc_bind_objects(mdc_ctx* ctx, const UndistorterFOV* fov, const PhotometricU
 }
 
 void mdc_fov_model_of(const UndistorterFOV& u, mdc_fov_model* m) {
+  if (u.lensModel() != 0) {  // a RadTan / EquiDistant camera has no FOV model: all zeros (mdch_fov_mdcn_model gives its own)
+    memset(m, 0, sizeof *m);
+    return;
+  }
   for (int i = 0; i < 5; i++) {
     m->in_calib[i] = MdcHostAccess::calib_in(u)[i];
     m->out_calib[i] = MdcHostAccess::calib_out(u)[i];
@@ -66,6 +71,40 @@ void mdc_fov_model_of(const UndistorterFOV& u, mdc_fov_model* m) {
 extern "C" {
 
 void mdch_fov_model(const mdch_fov* h, mdc_fov_model* m) try { mdc_fov_model_of(*h->u, m); } catch (...) {}
+
+int mdch_fov_lens_model(const mdch_fov* h, int* kind, float k[4]) try {
+  *kind = h->u->lensModel();
+  for (int i = 0; i < 4; i++) k[i] = h->u->lensParameters()[i];
+  return h->u->isValid() ? 1 : 0;
+} catch (...) { return {}; }
+
+int mdch_fov_mdcn_model(const mdch_fov* h, mdcn_model* m) try {
+  const UndistorterFOV& u = *h->u;
+  memset(m, 0, sizeof *m);
+  const float* in = MdcHostAccess::calib_in(u);
+  if (!u.isValid() || (u.lensModel() == 0 && in[4] != 0)) return 0;
+  m->kind = u.lensModel();
+  m->in_w = u.getInputDims()[0];
+  m->in_h = u.getInputDims()[1];
+  m->out_w = u.getOutputDims()[0];
+  m->out_h = u.getOutputDims()[1];
+  if (u.lensModel() == 0) {  // FOV with omega 0: the pinhole, with InputModel's steps
+    m->fx = in[0] * m->in_w;
+    m->fy = in[1] * m->in_h;
+    m->cx = in[2] * m->in_w - 0.5;
+    m->cy = in[3] * m->in_h - 0.5;
+  } else {
+    const float* cam = MdcHostAccess::lens_cam(u);
+    m->fx = cam[0], m->fy = cam[1], m->cx = cam[2], m->cy = cam[3];
+    for (int i = 0; i < 4; i++) m->k[i] = u.lensParameters()[i];
+  }
+  const float* out = MdcHostAccess::calib_out(u);  // pixel units derived as every consumer derives them (make_distort_model's steps)
+  m->ofx = out[0] * m->out_w;
+  m->ofy = out[1] * m->out_h;
+  m->ocx = out[2] * m->out_w - 0.5f;
+  m->ocy = out[3] * m->out_h - 0.5f;
+  return 1;
+} catch (...) { return {}; }
 
 mdch_fov* mdch_fov_create(const char* camera_txt) try {
   mdch_fov* h = new mdch_fov;
