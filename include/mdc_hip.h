@@ -386,7 +386,10 @@ MDC_API int mdc_undistort_batch_device_f32(mdc_ctx* ctx, const float* d_in, floa
 
 /* 2x2 box pyramid (BASELINE.json config 5; NOT in the reference -- definition in
  * DESIGN.md): for each of nframes w*h f32 images writes levels 1..levels-1 into
- * d_levels[l-1] (each nframes*(w>>l)*(h>>l) f32).  levels counts level 0. */
+ * d_levels[l-1] (each nframes*(w>>l)*(h>>l) f32).  levels counts level 0.
+ * A level that would be empty (w>>l or h>>l == 0 for some l < levels) is MDC_ERR_ARG, from this call,
+ * mdc_process_pyramid_batch_device and mdc_process_pyramid_gradients_batch_device alike, and nothing is
+ * enqueued: the deepest pyramid of a 3x3 image has levels = 2. */
 MDC_API int mdc_pyramid_batch_device(mdc_ctx* ctx, const float* d_base, int w, int h, int levels, float* const* d_levels,
                              int64_t nframes, void* stream);
 

@@ -283,6 +283,14 @@ int enqueue_process(mdc_ctx* c, const uint8_t* d_in, float* d_out, int64_t nfram
   return MDC_OK;
 }
 
+// `levels` counts level 0, the w x h image: a level that would be empty is an argument error of all three pyramid calls, found
+// before anything is enqueued
+int check_pyramid_levels(mdc_ctx* c, int w, int h, int levels) {
+  for (int l = 0; l < levels; l++)
+    if (l > 30 || (w >> l) < 1 || (h >> l) < 1) return fail(c, MDC_ERR_ARG, "level %d of a %dx%d image is empty", l, w, h);
+  return MDC_OK;
+}
+
 // base + box levels (+ gradient images when d_dI / d_abs_squared_grad are given) of nframes device-resident raw frames, in chunks;
 // lock held by the caller (mdc_process_pyramid_gradients_batch_device and the *_to_device pipeline, mdc_pipeline.hip)
 int enqueue_pyramid_gradients(mdc_ctx* c, const uint8_t* d_in, float* d_base, int levels, float* const* d_levels, float* const* d_dI,
@@ -293,12 +301,12 @@ int enqueue_pyramid_gradients(mdc_ctx* c, const uint8_t* d_in, float* d_base, in
   const int w0 = rect ? c->out_w : (c->in_w > 0 ? c->in_w : c->rm_in_w), h0 = rect ? c->out_h : (c->in_h > 0 ? c->in_h : c->rm_in_h);
   const int iw = (rect || c->in_w <= 0) ? c->rm_in_w : c->in_w, ih = (rect || c->in_h <= 0) ? c->rm_in_h : c->in_h;
   if (w0 <= 0 || h0 <= 0 || iw <= 0 || ih <= 0) return fail(c, MDC_ERR_STATE, "frame size unknown");
+  if (int rc = check_pyramid_levels(c, w0, h0, levels)) return rc;
   int lw[8], lh[8];
   size_t level_bytes = 0;
   for (int l = 0; l < levels; l++) {
     lw[l] = w0 >> l;
     lh[l] = h0 >> l;
-    if (lw[l] < 1 || lh[l] < 1) return fail(c, MDC_ERR_ARG, "level %d of a %dx%d image is empty", l, w0, h0);
     level_bytes += (size_t)lw[l] * lh[l] * sizeof(float);
   }
   // Frames per chunk.  Measured (tools/dso_rate.py, 1280 x 1024, 512 frames, profiles/r03_dso_rate.txt): 8 frames per chunk
@@ -751,12 +759,14 @@ int mdc_pyramid_batch_device(mdc_ctx* c, const float* d_base, int w, int h, int 
   if (!c) return MDC_ERR_ARG;
   if (!d_base || w <= 0 || h <= 0 || levels < 1 || nframes < 0 || (levels > 1 && !d_levels))
     return fail(c, MDC_ERR_ARG, "mdc_pyramid_batch_device: bad argument");
+  for (int l = 1; l < levels; l++)  // before anything is enqueued
+    if (!d_levels[l - 1]) return fail(c, MDC_ERR_ARG, "level %d buffer is NULL", l);
+  if (int rc = check_pyramid_levels(c, w, h, levels)) return rc;
   ReadLock lk(c->mu);
   DeviceGuard dg(c->device);
   hipStream_t s = (hipStream_t)stream;
   const float* src = d_base;
   for (int l = 1; l < levels; l++) {
-    if (!d_levels[l - 1]) return fail(c, MDC_ERR_ARG, "level %d buffer is NULL", l);
     MDC_HIP(c, launch_pyramid_level(src, d_levels[l - 1], w >> (l - 1), h >> (l - 1), nframes, s));
     src = d_levels[l - 1];
   }
@@ -775,6 +785,8 @@ int mdc_process_pyramid_batch_device(mdc_ctx* c, const uint8_t* d_in, float* d_b
   hipStream_t s = (hipStream_t)stream;
   const bool rect = (flags & MDC_RECTIFY) != 0;
   const int w = rect ? c->out_w : (c->in_w > 0 ? c->in_w : c->rm_in_w), h = rect ? c->out_h : (c->in_h > 0 ? c->in_h : c->rm_in_h);
+  if (w > 0 && h > 0)  // (an unknown frame size is enqueue_process's to refuse)
+    if (int rc = check_pyramid_levels(c, w, h, levels)) return rc;
   float* pyr[3] = {levels > 1 ? d_levels[0] : nullptr, levels > 2 ? d_levels[1] : nullptr, levels > 3 ? d_levels[2] : nullptr};
   bool fused = false;
   int rc = enqueue_process(c, d_in, d_base, nframes, flags, s, levels > 1 ? pyr : nullptr, &fused);
