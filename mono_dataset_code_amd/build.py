@@ -491,6 +491,12 @@ def build_fault_injection():
     return build_variant("badprov", ["MDC_EXP_HUFF_BAD_PROVISIONAL=1"])
 
 
+def build_huff_rounds():
+    """libmdc_hip with MDC_EXP_HUFF_ROUNDS: the one-workgroup-per-frame Huffman kernel reports its relaxation rounds in the status
+    word's upper bits (tests/test_jdec.py); right records."""
+    return build_variant("huffrounds", ["MDC_EXP_HUFF_ROUNDS=1"])
+
+
 def build_all(force=False):
     build_hip(force)
     build_host(force)
@@ -508,6 +514,7 @@ def build_all(force=False):
     build_lens(force)
     build_debug()
     build_fault_injection()
+    build_huff_rounds()
     return LIB_HIP, LIB_HOST, LIB_MULTI
 
 

@@ -436,7 +436,7 @@ bool jpeg_gray8(const unsigned char* d, size_t n, unsigned char* out, size_t cap
               if (t < 0 || t > 11) return fail(err, "JPEG: bad DC code");
               comp[c].pred += t ? extend(b.get(t), t) : 0;
               if (blk) blk[0] = (int16_t)comp[c].pred;
-              else if (luma) coef[0] = comp[c].pred * q[0];
+              else if (luma) coef[0] = (int16_t)comp[c].pred * q[0];  // (the coefficient is the predictor's low 16 bits, as in the record and in libjpeg's JCOEF)
               bool dc_only = true;
               const Huff& act = hdr.ac[comp[c].ta];
               for (int i = 1; i < 64;) {

@@ -51,11 +51,9 @@ def sequential_decode(stream, pitch, rows):
     off = H["ecs_off"]
     assert not stream[off + ecs: off + ecs + 16].any(), "16 zero bytes follow the entropy-coded segment"
     data = bytes(stream[off: off + ecs + 16])
-    total = len(data) * 8
-    val = int.from_bytes(data, "big")
 
-    def peek(p, n):
-        return (val >> (total - p - n)) & ((1 << n) - 1) if n else 0
+    def peek(p, n):  # n <= 25 bits at bit p (the callers ask for 11, 5 and a size <= 15): they lie in the four bytes from p >> 3 on
+        return (int.from_bytes(data[p >> 3: (p >> 3) + 4], "big") >> (32 - (p & 7) - n)) & ((1 << n) - 1) if n else 0
 
     hy, vy = H["hy"], H["vy"]
     mx, my = (w + 8 * hy - 1) // (8 * hy), (h + 8 * vy - 1) // (8 * vy)
@@ -96,7 +94,7 @@ def sequential_decode(stream, pitch, rows):
                         v = bits if size == 0 or bits >> (size - 1) else bits - (1 << size) + 1
                     if not ac:
                         dc[c] += v
-                        out[0] = dc[c]
+                        out[0] = ((dc[c] + 32768) & 0xFFFF) - 32768  # (the record keeps the predictor's low 16 bits)
                         z = 1
                     elif size == 0:
                         z = z + 16 if run == 15 else 64
