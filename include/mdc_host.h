@@ -30,6 +30,7 @@ MDC_API void mdch_fov_dims(const mdch_fov*, int d4[4]);      /* getInputDims(), 
 MDC_API void mdch_fov_intrinsics(const mdch_fov*, float out29[29]);
 MDC_API int mdch_fov_remap(const mdch_fov*, float* remap_x, float* remap_y); /* copies the tables; 0 if none */
 MDC_API void mdch_fov_distort(mdch_fov*, float* x, float* y, int n);         /* distortCoordinates() */
+MDC_API void mdch_fov_undistort_points(mdch_fov*, float* x, float* y, int n); /* undistortCoordinates(): raw -> rectified */
 MDC_API void mdch_fov_undistort_f32(const mdch_fov*, const float* in, float* out, int n_in, int n_out); /* undistort<float> */
 MDC_API void mdch_fov_undistort_u8(const mdch_fov*, const unsigned char* in, float* out, int n_in, int n_out);
 

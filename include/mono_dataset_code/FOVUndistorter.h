@@ -37,6 +37,12 @@ class MDC_API UndistorterFOV {
   // In place: rectified pixel coordinates -> raw (distorted) pixel coordinates.
   void distortCoordinates(float* in_x, float* in_y, int n);
 
+  // In place, the other way: raw (distorted) pixel coordinates -> rectified pixel coordinates, for every lens kind the class
+  // reads (not in the reference).  A point the model cannot bring back -- FOV: raw radius times omega not below pi/2;
+  // EquiDistant: an angle outside [0, pi/2); RadTan: an iteration that left the finite numbers -- comes out as NaN in both
+  // coordinates.  Calls of at least MDC_UNDISTORT_GPU_MIN points (default 65536) run on the device, with the host loop's bits.
+  void undistortCoordinates(float* x, float* y, int n);
+
   Eigen::Matrix3f getK_rect() const { return k_rect_; }
   Eigen::Matrix3f getK_org() const { return k_org_; }
   float getOmega() const { return calib_in_[4]; }

@@ -7,6 +7,7 @@
                                         libmdc_pnglz.so, libmdc_pngd.so, libmdc_pngdx.so: one translation unit each over shared core
                                         headers, all by one rule (_build_codec), outside libmdc_hip.so's build identity
   libmdc_lens.so, hipcc, gfx950         the RadTan / EquiDistant / pinhole lens models (include/mdc_lens.h), by the same rule
+  libmdc_lensinv.so, hipcc, gfx950      the same models and FOV run backwards, raw -> rectified (include/mdc_lensinv.h), by the same rule
   bin/                                  the programs; tests/native/ programs are built into a place the tests name
 
 All land next to this file so they travel with the source tree to the GPU box.
@@ -41,6 +42,7 @@ HOST_DEPS = HOST_SOURCES + [os.path.join(HOST, "mdc_host_exports.map"), os.path.
                             os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"), os.path.join(CSRC, "png_inflate_core.h"),
                             os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h"),
                             os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_host.h"), os.path.join(INC, "mdc_lens.h"),
+                            os.path.join(INC, "mdc_lensinv.h"), os.path.join(CSRC, "lens_inverse_model.h"),
                             os.path.join(CSRC, "lens_point_model.h"), os.path.join(CSRC, "fov_point_model.h"),
                             os.path.join(INC, "mono_dataset_code", "FOVUndistorter.h"),
                             os.path.join(INC, "mono_dataset_code", "PhotometricUndistorter.h"),
@@ -428,6 +430,28 @@ def build_lens_core_program(out, sanitize=True):
     return _build_native_program("lens_core.cpp", out, sanitize, flags=LENS_FP_FLAGS)
 
 
+LIB_LENSINV = os.path.join(PKG, "libmdc_lensinv.so")
+LENSINV_SOURCE = os.path.join(CSRC, "mdc_lensinv.hip")
+LENSINV_MODEL = os.path.join(CSRC, "lens_inverse_model.h")  # the inverse arithmetic: libmdc_lensinv.so, libmdc_host.so and a CPU test program
+LENSINV_EXPORT_MAP = os.path.join(CSRC, "mdc_lensinv_exports.map")
+
+
+def build_lensinv(force=False):
+    """libmdc_lensinv.so: raw pixel -> rectified pixel through the pinhole / RadTan / EquiDistant / FOV lens models on the device
+    (include/mdc_lensinv.h) -- one translation unit over the header it shares with libmdc_host.so and the CPU test program; it links
+    nothing of this project, and it is outside libmdc_hip.so's build identity.  libmdc_host.so loads it at run time for bulk
+    undistortCoordinates() calls, nothing links it."""
+    return _build_codec(LIB_LENSINV, LENSINV_SOURCE, [LENSINV_MODEL, LENS_MODEL, FOV_MODEL, os.path.join(INC, "mdc_lensinv.h")], LENSINV_EXPORT_MAP, force=force,
+                        extra_flags=LENS_FP_FLAGS)
+
+
+def build_lens_inverse_core_program(out, sanitize=True):
+    """tests/native/lens_inverse_core.cpp: lens_inverse_model.h (the inverse arithmetic and the inverse tables' border rules) as a
+    stand-alone program (its own main), under AddressSanitizer and UndefinedBehaviorSanitizer (tests/test_lens_inverse_cpu.py).
+    Pure host code."""
+    return _build_native_program("lens_inverse_core.cpp", out, sanitize, flags=LENS_FP_FLAGS)
+
+
 LIB_MULTI = os.path.join(PKG, "libmdc_multi.so")
 MULTI_SOURCE = os.path.join(CSRC, "mdc_multi.hip")
 
@@ -512,6 +536,7 @@ def build_all(force=False):
     build_pngd(force)
     build_pngdx(force)
     build_lens(force)
+    build_lensinv(force)
     build_debug()
     build_fault_injection()
     build_huff_rounds()

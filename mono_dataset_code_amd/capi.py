@@ -80,10 +80,12 @@ class FovModel(C.Structure):
 
 LENS_PINHOLE, LENS_RADTAN, LENS_EQUIDISTANT = 0, 1, 2  # MDCN_PINHOLE, MDCN_RADTAN, MDCN_EQUIDISTANT
 LENS_NAMES = {0: "FOV / pinhole", 1: "RadTan", 2: "EquiDistant"}  # UndistorterFOV.lens_model()
+LENSINV_PINHOLE, LENSINV_RADTAN, LENSINV_EQUIDISTANT, LENSINV_FOV = 0, 1, 2, 3  # MDCU_PINHOLE, MDCU_RADTAN, MDCU_EQUIDISTANT, MDCU_FOV
 
 
 class LensModel(C.Structure):
-    """include/mdc_lens.h: mdcn_model -- a raw camera (pinhole, RadTan or EquiDistant) and the rectified pinhole, in pixels."""
+    """include/mdc_lens.h: mdcn_model -- a raw camera (pinhole, RadTan or EquiDistant) and the rectified pinhole, in pixels.
+    include/mdc_lensinv.h: mdcu_model has the same 17 words, and the kind LENSINV_FOV with k[0] = omega beside the three."""
     _fields_ = [("kind", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k", C.c_float * 4),
                 ("in_w", C.c_int), ("in_h", C.c_int), ("ofx", C.c_float), ("ofy", C.c_float), ("ocx", C.c_float), ("ocy", C.c_float),
                 ("out_w", C.c_int), ("out_h", C.c_int)]
@@ -243,6 +245,7 @@ HOST_API = {  # include/mdc_host.h (libmdc_host.so)
     "mdch_fov_intrinsics": (None, [_vp, _vp]),
     "mdch_fov_remap": (_i, [_vp, _vp, _vp]),
     "mdch_fov_distort": (None, [_vp, _vp, _vp, _i]),
+    "mdch_fov_undistort_points": (None, [_vp, _vp, _vp, _i]),
     "mdch_fov_undistort_f32": (None, [_vp, _vp, _vp, _i, _i]),
     "mdch_fov_undistort_u8": (None, [_vp, _vp, _vp, _i, _i]),
     "mdch_fov_model": (None, [_vp, _P(FovModel)]),
@@ -403,6 +406,12 @@ LENS_API = {  # include/mdc_lens.h (libmdc_lens.so: the pinhole / RadTan / EquiD
     "mdcn_distort_points_host": (_i, [_i, _P(LensModel), _vp, _vp, _i64]),
     "mdcn_remap_device": (_i, [_P(LensModel), _vp, _vp, _vp, _vp]),
 }
+LENSINV_API = {  # include/mdc_lensinv.h (libmdc_lensinv.so: the lens models run backwards, raw -> rectified, a library of its own)
+    "mdcu_last_error": (_cp, []),
+    "mdcu_undistort_points_device": (_i, [_P(LensModel), _vp, _vp, _i64, _vp]),
+    "mdcu_undistort_points_host": (_i, [_i, _P(LensModel), _vp, _vp, _i64]),
+    "mdcu_inverse_remap_device": (_i, [_P(LensModel), _vp, _vp, _vp, _vp]),
+}
 HIP_SYMBOLS, HOST_SYMBOLS, BENCH_SYMBOLS = list(HIP_API), list(HOST_API), list(BENCH_API)
 
 LIB_BENCH_PATH = os.path.join(_PKG, "libmdc_bench.so")
@@ -415,6 +424,7 @@ LIB_PNGLZ_PATH = os.path.join(_PKG, "libmdc_pnglz.so")
 LIB_PNGD_PATH = os.path.join(_PKG, "libmdc_pngd.so")
 LIB_PNGDX_PATH = os.path.join(_PKG, "libmdc_pngdx.so")
 LIB_LENS_PATH = os.path.join(_PKG, "libmdc_lens.so")
+LIB_LENSINV_PATH = os.path.join(_PKG, "libmdc_lensinv.so")
 _hip = None
 _host = None
 
@@ -480,6 +490,7 @@ pnglz_lib = _lazy_lib(LIB_PNGLZ_PATH, PNGLZ_API,
 pngd_lib = _lazy_lib(LIB_PNGD_PATH, PNGD_API, "libmdc_pngd.so: the PNG decoder for frames whose zlib streams are in device or host memory (include/mdc_pngd.h).")
 pngdx_lib = _lazy_lib(LIB_PNGDX_PATH, PNGDX_API, "libmdc_pngdx.so: the PNG decoder with a parallel inflate for streams with matches (include/mdc_pngdx.h).")
 lens_lib = _lazy_lib(LIB_LENS_PATH, LENS_API, "libmdc_lens.so: the pinhole / RadTan / EquiDistant lens models on the device (include/mdc_lens.h).")
+lensinv_lib = _lazy_lib(LIB_LENSINV_PATH, LENSINV_API, "libmdc_lensinv.so: raw -> rectified points through every lens model, on the device (include/mdc_lensinv.h).")
 
 
 def hip_lib():
@@ -1151,6 +1162,27 @@ class UndistorterFOV:
         assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size
         self._L.mdch_fov_distort(self._h, _np_ptr(x), _np_ptr(y), x.size)
 
+    def undistort_coordinates(self, x, y):
+        """undistortCoordinates(): raw pixel coordinates -> rectified ones, in place (NaN where the model cannot bring a point back)"""
+        assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size and x.flags.c_contiguous and y.flags.c_contiguous
+        self._L.mdch_fov_undistort_points(self._h, _np_ptr(x), _np_ptr(y), x.size)
+
+    def inverse_model(self):
+        """the cameras in pixels as a LensModel for capi.LensInverse, of the kind LENSINV_RADTAN / LENSINV_EQUIDISTANT, or LENSINV_FOV
+        with k[0] = omega for a FOV / pinhole camera (pixel units by the class's own float and double steps); raises for an invalid
+        object"""
+        if not self.is_valid():
+            raise MdcError(ERR_ARG, "no inverse model for an invalid object")
+        if self.lens_model()[0] != 0:
+            return self.mdcn_model()  # kinds 1 and 2 keep their values
+        f = self.model()
+        F, w, h = np.float32, np.float32(f.in_w), np.float32(f.in_h)
+        c = [F(v) for v in f.in_calib]
+        cam = [c[0] * w, c[1] * h, F(np.float64(c[2] * w) - 0.5), F(np.float64(c[3] * h) - 0.5), c[4], 0, 0, 0]
+        o, ow, oh = [F(v) for v in f.out_calib], np.float32(f.out_w), np.float32(f.out_h)
+        rect = (o[0] * ow, o[1] * oh, o[2] * ow - F(0.5), o[3] * oh - F(0.5))
+        return LensModel.make(LENSINV_FOV, cam, rect, (f.in_w, f.in_h), (f.out_w, f.out_h))
+
     def undistort(self, img, out):
         fn = self._L.mdch_fov_undistort_f32 if img.dtype == np.float32 else self._L.mdch_fov_undistort_u8
         fn(self._h, _np_ptr(img), _np_ptr(out), img.size, out.size)
@@ -1468,6 +1500,32 @@ class Lens:
     def remap_device(self, d_rx, d_ry, d_black, stream=0):
         """the model's out_w x out_h remap tables into device arrays, *d_black (an int32 on the device) = 1 if any entry is black"""
         self._check(self._L.mdcn_remap_device(C.byref(self.model), d_rx, d_ry, d_black, _stream(stream)))
+
+
+class LensInverse:
+    """The calls of include/mdc_lensinv.h on one LensModel (UndistorterFOV.inverse_model(), or LensModel.make with a LENSINV_* kind)."""
+
+    def __init__(self, model):
+        self._L = lensinv_lib()
+        self.model = model
+
+    def _check(self, rc):
+        if rc < 0:
+            raise MdcError(int(rc), self._L.mdcu_last_error().decode())
+        return rc
+
+    def undistort_points_device(self, d_x, d_y, n, stream=0):
+        """n raw points in the device arrays at d_x, d_y -> rectified, in place; enqueues on `stream` and does not synchronise"""
+        self._check(self._L.mdcu_undistort_points_device(C.byref(self.model), d_x, d_y, int(n), _stream(stream)))
+
+    def undistort_points_host(self, x, y, device=-1):
+        """float32 arrays, in place, blocking; untouched when the call fails (it raises)"""
+        assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size and x.flags.c_contiguous and y.flags.c_contiguous
+        self._check(self._L.mdcu_undistort_points_host(int(device), C.byref(self.model), _np_ptr(x), _np_ptr(y), x.size))
+
+    def inverse_remap_device(self, d_ux, d_uy, d_outside, stream=0):
+        """the model's in_w x in_h inverse tables into device arrays, *d_outside (an int32 on the device) = 1 if any entry is (-1, -1)"""
+        self._check(self._L.mdcu_inverse_remap_device(C.byref(self.model), d_ux, d_uy, d_outside, _stream(stream)))
 
 
 def huffman_lengths_device(d_hist, nsym, limit, d_lengths, stream=None):

@@ -26,6 +26,8 @@
 #include "host_device.h"
 #include "../fov_point_model.h"  // atanf_host_libm: the restatement the device runs, checked against THIS process's libm below
 #include "../lens_point_model.h"  // the RadTan / EquiDistant arithmetic and the crop rule, shared with libmdc_lens.so's kernels
+#include "mdc_lensinv.h"
+#include "../lens_inverse_model.h"  // raw -> rectified for every kind, shared with libmdc_lensinv.so's kernels
 
 namespace {
 
@@ -567,6 +569,108 @@ void UndistorterFOV::distortCoordinates(float* in_x, float* in_y, int n) {
     std::fprintf(stderr, "UndistorterFOV::distortCoordinates: the GPU call failed (%s); computing %d points on the host\n", mdc_last_error(gpu_), n);
   }
   warp_points(calib_in_, in_w_, in_h_, calib_out_, out_w_, out_h_, in_x, in_y, n);
+}
+
+// ---- raw -> rectified points (csrc/lens_inverse_model.h holds the arithmetic) --------------------------------------------
+
+namespace {
+
+void unwarp_points(int kind, const mdc::LensInverseModel& m, float* xs, float* ys, long n) {
+  if (kind == mdc::LENSINV_RADTAN)
+    for (long i = 0; i < n; i++) mdc::lens_undistort_point<mdc::LENSINV_RADTAN>(m, xs[i], ys[i]);
+  else if (kind == mdc::LENSINV_EQUIDISTANT)
+    for (long i = 0; i < n; i++) mdc::lens_undistort_point<mdc::LENSINV_EQUIDISTANT>(m, xs[i], ys[i]);
+  else
+    for (long i = 0; i < n; i++) mdc::lens_undistort_point<mdc::LENSINV_FOV>(m, xs[i], ys[i]);
+}
+
+// libmdc_lensinv.so's bulk call, loaded the way libmdc_lens.so's is: the file next to this library (or the one MDC_LIB_LENSINV
+// names), opened once per process and never closed; 0 when it is not there.
+typedef int (*LensUndistortHost)(int, const mdcu_model*, float*, float*, int64_t);
+struct LensInvApi {
+  LensUndistortHost undistort_points_host;
+  const char* (*last_error)();
+};
+
+const LensInvApi* load_lensinv_api() {
+  std::string path;
+  if (const char* e = std::getenv("MDC_LIB_LENSINV")) {
+    path = e;
+  } else {
+    Dl_info info;
+    if (dladdr((void*)&mdc_host::open_device_context, &info) && info.dli_fname) {
+      path = info.dli_fname;
+      const size_t sl = path.rfind('/');
+      path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
+    }
+    path += "libmdc_lensinv.so";
+  }
+  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);
+  if (!lib) return 0;
+  static LensInvApi api;
+  api.undistort_points_host = (LensUndistortHost)dlsym(lib, "mdcu_undistort_points_host");
+  api.last_error = (const char* (*)())dlsym(lib, "mdcu_last_error");
+  return api.undistort_points_host && api.last_error ? &api : 0;
+}
+
+const LensInvApi* lensinv_api() {
+  static const LensInvApi* api = load_lensinv_api();
+  return api;
+}
+
+}  // namespace
+
+void UndistorterFOV::undistortCoordinates(float* x, float* y, int n) {
+  if (!valid_) {
+    std::printf("ERROR: invalid UndistorterFOV!\n");
+    return;
+  }
+  // The same rule as distortCoordinates: small counts run the loop here, bulk calls go to the device, whose kernel runs the same
+  // header with the same flags (no libm is involved in this direction: the tangent is the header's own).  MDC_UNDISTORT_GPU_MIN
+  // overrides the threshold (0 = never on the device).
+  static const long gpu_min = [] {
+    const char* e = std::getenv("MDC_UNDISTORT_GPU_MIN");
+    return e ? std::atol(e) : 65536l;
+  }();
+  const LensState* const ls = find_lens_state(this);
+  mdcu_model m;
+  if (ls) {
+    m.kind = ls->kind;  // MDCU_RADTAN / MDCU_EQUIDISTANT == the class's kinds
+    m.fx = ls->cam[0], m.fy = ls->cam[1], m.cx = ls->cam[2], m.cy = ls->cam[3];
+    for (int i = 0; i < 4; i++) m.k[i] = ls->k[i];
+  } else {
+    const InputModel im(calib_in_, in_w_, in_h_);
+    m.kind = MDCU_FOV;
+    m.fx = im.fx, m.fy = im.fy, m.cx = im.cx, m.cy = im.cy;
+    m.k[0] = im.omega;
+    m.k[1] = m.k[2] = m.k[3] = 0;
+  }
+  mdc::LensInverseModel lm;
+  lm.fx = m.fx, lm.fy = m.fy, lm.cx = m.cx, lm.cy = m.cy;
+  for (int i = 0; i < 4; i++) lm.k[i] = m.k[i];
+  lm.d2t = m.kind == MDCU_FOV ? mdc::lens_inverse_d2t(m.k[0]) : 0.0f;
+  lm.ofx = calib_out_[0] * out_w_;  // pixel units derived from the stored normalised values with lens_set_rectified's float steps
+  lm.ofy = calib_out_[1] * out_h_;
+  lm.ocx = calib_out_[2] * out_w_ - 0.5f;
+  lm.ocy = calib_out_[3] * out_h_ - 0.5f;
+  m.in_w = in_w_, m.in_h = in_h_;
+  m.ofx = lm.ofx, m.ofy = lm.ofy, m.ocx = lm.ocx, m.ocy = lm.ocy;
+  m.out_w = out_w_, m.out_h = out_h_;
+  if (gpu_min > 0 && n >= gpu_min) {
+    const LensInvApi* api = lensinv_api();
+    mdc_info info;
+    if (api && gpu_ && mdc_get_info(gpu_, &info) == MDC_OK) {
+      if (api->undistort_points_host(info.device, &m, x, y, n) == MDCU_OK) return;
+      // the call leaves the coordinates untouched when it fails (they are copied back last): say so and do the work here
+      std::fprintf(stderr, "UndistorterFOV::undistortCoordinates: the GPU call failed (%s); computing %d points on the host\n", api->last_error(), n);
+    } else {
+      static bool said = false;
+      if (!said) std::fprintf(stderr, "UndistorterFOV::undistortCoordinates: %s; bulk calls are computed on the host (same results)\n",
+                              api ? "no GPU context" : "libmdc_lensinv.so could not be loaded (MDC_LIB_LENSINV names another file)");
+      said = true;
+    }
+  }
+  unwarp_points(m.kind, lm, x, y, n);
 }
 
 namespace {

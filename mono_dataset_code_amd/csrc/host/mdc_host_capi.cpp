@@ -144,6 +144,7 @@ int mdch_fov_remap(const mdch_fov* h, float* rx, float* ry) try {
   return 1;
 } catch (...) { return {}; }  // no exception leaves the C facade
 void mdch_fov_distort(mdch_fov* h, float* x, float* y, int n) try { h->u->distortCoordinates(x, y, n); } catch (...) {}
+void mdch_fov_undistort_points(mdch_fov* h, float* x, float* y, int n) try { h->u->undistortCoordinates(x, y, n); } catch (...) {}
 void mdch_fov_undistort_f32(const mdch_fov* h, const float* in, float* out, int n_in, int n_out) try {
   h->u->undistort<float>(in, out, n_in, n_out);
 } catch (...) {}
