@@ -7,7 +7,8 @@
                                         libmdc_pnglz.so, libmdc_pngd.so, libmdc_pngdx.so: one translation unit each over shared core
                                         headers, all by one rule (_build_codec), outside libmdc_hip.so's build identity
   libmdc_lens.so, hipcc, gfx950         the RadTan / EquiDistant / pinhole lens models (include/mdc_lens.h), by the same rule
-  libmdc_lensinv.so, hipcc, gfx950      the same models and FOV run backwards, raw -> rectified (include/mdc_lensinv.h), by the same rule
+  libmdc_lensinv.so, hipcc, gfx950      the same models and FOV run backwards, raw -> rectified (include/mdc_lensinv.h), by the same rule;
+                                        the two share their kernels and host side (csrc/lens_points_shell.h) and differ in the arithmetic
   bin/                                  the programs; tests/native/ programs are built into a place the tests name
 
 All land next to this file so they travel with the source tree to the GPU box.
@@ -39,7 +40,7 @@ HOST_SOURCES = [os.path.join(HOST, f) for f in (
 HOST_DEPS = HOST_SOURCES + [os.path.join(HOST, "mdc_host_exports.map"), os.path.join(HOST, "gray_png.h"), os.path.join(HOST, "host_device.h"),
                             os.path.join(HOST, "image_codecs.h"), os.path.join(HOST, "image_codecs_internal.h"), os.path.join(HOST, "image_codecs_jpeg.h"), os.path.join(HOST, "zip_reader.h"),
                             os.path.join(HOST, "frame_source.h"), os.path.join(HOST, "decode_pool.h"), os.path.join(HOST, "prefetch_cache.h"),
-                            os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"), os.path.join(CSRC, "png_inflate_core.h"),
+                            os.path.join(HOST, "device_lanes.h"), os.path.join(HOST, "batch_run.h"), os.path.join(HOST, "sibling_library.h"), os.path.join(CSRC, "png_inflate_core.h"),
                             os.path.join(INC, "mono_dataset_code", "BenchmarkDatasetReader.h"),
                             os.path.join(INC, "mdc_hip.h"), os.path.join(INC, "mdc_host.h"), os.path.join(INC, "mdc_lens.h"),
                             os.path.join(INC, "mdc_lensinv.h"), os.path.join(CSRC, "lens_inverse_model.h"),
@@ -413,15 +414,16 @@ LIB_LENS = os.path.join(PKG, "libmdc_lens.so")
 LENS_SOURCE = os.path.join(CSRC, "mdc_lens.hip")
 LENS_MODEL = os.path.join(CSRC, "lens_point_model.h")  # the lens arithmetic and the crop rule: libmdc_lens.so, libmdc_host.so and a CPU test program
 FOV_MODEL = os.path.join(CSRC, "fov_point_model.h")  # atanf_host_libm (read here, never edited: it is part of libmdc_hip.so's identity)
+LENS_SHELL = os.path.join(CSRC, "lens_points_shell.h")  # what the two lens libraries share: the kernels, the launches, the calls' host side
 LENS_EXPORT_MAP = os.path.join(CSRC, "mdc_lens_exports.map")
 LENS_FP_FLAGS = ["-ffp-contract=off", "-fno-fast-math"]  # IEEE single precision, no FMA: the device gives the host's bits
 
 
 def build_lens(force=False):
     """libmdc_lens.so: the pinhole / RadTan / EquiDistant lens models on the device (include/mdc_lens.h) -- one translation unit over
-    the header it shares with libmdc_host.so and the CPU test program; it links nothing of this project, and it is outside
-    libmdc_hip.so's build identity.  libmdc_host.so loads it at run time for bulk distortCoordinates() calls, nothing links it."""
-    return _build_codec(LIB_LENS, LENS_SOURCE, [LENS_MODEL, FOV_MODEL, os.path.join(INC, "mdc_lens.h")], LENS_EXPORT_MAP, force=force, extra_flags=LENS_FP_FLAGS)
+    the header it shares with libmdc_host.so and the CPU test program and the shell it shares with mdc_lensinv.hip; it links nothing
+    of this project, and it is outside libmdc_hip.so's build identity.  libmdc_host.so loads it at run time for bulk distortCoordinates() calls, nothing links it."""
+    return _build_codec(LIB_LENS, LENS_SOURCE, [LENS_SHELL, LENS_MODEL, FOV_MODEL, os.path.join(INC, "mdc_lens.h")], LENS_EXPORT_MAP, force=force, extra_flags=LENS_FP_FLAGS)
 
 
 def build_lens_core_program(out, sanitize=True):
@@ -438,10 +440,10 @@ LENSINV_EXPORT_MAP = os.path.join(CSRC, "mdc_lensinv_exports.map")
 
 def build_lensinv(force=False):
     """libmdc_lensinv.so: raw pixel -> rectified pixel through the pinhole / RadTan / EquiDistant / FOV lens models on the device
-    (include/mdc_lensinv.h) -- one translation unit over the header it shares with libmdc_host.so and the CPU test program; it links
-    nothing of this project, and it is outside libmdc_hip.so's build identity.  libmdc_host.so loads it at run time for bulk
+    (include/mdc_lensinv.h) -- one translation unit over the header it shares with libmdc_host.so and the CPU test program and the
+    shell it shares with mdc_lens.hip; it links nothing of this project, and it is outside libmdc_hip.so's build identity.  libmdc_host.so loads it at run time for bulk
     undistortCoordinates() calls, nothing links it."""
-    return _build_codec(LIB_LENSINV, LENSINV_SOURCE, [LENSINV_MODEL, LENS_MODEL, FOV_MODEL, os.path.join(INC, "mdc_lensinv.h")], LENSINV_EXPORT_MAP, force=force,
+    return _build_codec(LIB_LENSINV, LENSINV_SOURCE, [LENS_SHELL, LENSINV_MODEL, LENS_MODEL, FOV_MODEL, os.path.join(INC, "mdc_lensinv.h")], LENSINV_EXPORT_MAP, force=force,
                         extra_flags=LENS_FP_FLAGS)
 
 

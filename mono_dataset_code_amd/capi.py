@@ -1476,56 +1476,58 @@ class PngDecoder:
         return status[:n], d_frames.value
 
 
-class Lens:
-    """The calls of include/mdc_lens.h on one LensModel (UndistorterFOV.mdcn_model(), or LensModel.make)."""
+class _LensCalls:
+    """What Lens and LensInverse share: one LensModel, and the calls of one library's `_prefix` on it."""
 
     def __init__(self, model):
-        self._L = lens_lib()
-        self.model = model
+        self._L, self.model = self._lib(), model
 
     def _check(self, rc):
         if rc < 0:
-            raise MdcError(int(rc), self._L.mdcn_last_error().decode())
+            raise MdcError(int(rc), getattr(self._L, self._prefix + "last_error")().decode())
         return rc
+
+    # the points call (third: n) and the table call (third: the flag's device address) have one shape
+    def _device_call(self, name, d_a, d_b, third, stream):
+        self._check(getattr(self._L, self._prefix + name)(C.byref(self.model), d_a, d_b, third, _stream(stream)))
+
+    def _host_call(self, name, x, y, device):
+        assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size and x.flags.c_contiguous and y.flags.c_contiguous
+        self._check(getattr(self._L, self._prefix + name)(int(device), C.byref(self.model), _np_ptr(x), _np_ptr(y), x.size))
+
+
+class Lens(_LensCalls):
+    """The calls of include/mdc_lens.h on one LensModel (UndistorterFOV.mdcn_model(), or LensModel.make)."""
+    _lib, _prefix = staticmethod(lens_lib), "mdcn_"
 
     def distort_points_device(self, d_x, d_y, n, stream=0):
         """n points in the device arrays at d_x, d_y, in place; enqueues on `stream` and does not synchronise"""
-        self._check(self._L.mdcn_distort_points_device(C.byref(self.model), d_x, d_y, int(n), _stream(stream)))
+        self._device_call("distort_points_device", d_x, d_y, int(n), stream)
 
     def distort_points_host(self, x, y, device=-1):
         """float32 arrays, in place, blocking; untouched when the call fails (it raises)"""
-        assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size and x.flags.c_contiguous and y.flags.c_contiguous
-        self._check(self._L.mdcn_distort_points_host(int(device), C.byref(self.model), _np_ptr(x), _np_ptr(y), x.size))
+        self._host_call("distort_points_host", x, y, device)
 
     def remap_device(self, d_rx, d_ry, d_black, stream=0):
         """the model's out_w x out_h remap tables into device arrays, *d_black (an int32 on the device) = 1 if any entry is black"""
-        self._check(self._L.mdcn_remap_device(C.byref(self.model), d_rx, d_ry, d_black, _stream(stream)))
+        self._device_call("remap_device", d_rx, d_ry, d_black, stream)
 
 
-class LensInverse:
+class LensInverse(_LensCalls):
     """The calls of include/mdc_lensinv.h on one LensModel (UndistorterFOV.inverse_model(), or LensModel.make with a LENSINV_* kind)."""
-
-    def __init__(self, model):
-        self._L = lensinv_lib()
-        self.model = model
-
-    def _check(self, rc):
-        if rc < 0:
-            raise MdcError(int(rc), self._L.mdcu_last_error().decode())
-        return rc
+    _lib, _prefix = staticmethod(lensinv_lib), "mdcu_"
 
     def undistort_points_device(self, d_x, d_y, n, stream=0):
         """n raw points in the device arrays at d_x, d_y -> rectified, in place; enqueues on `stream` and does not synchronise"""
-        self._check(self._L.mdcu_undistort_points_device(C.byref(self.model), d_x, d_y, int(n), _stream(stream)))
+        self._device_call("undistort_points_device", d_x, d_y, int(n), stream)
 
     def undistort_points_host(self, x, y, device=-1):
         """float32 arrays, in place, blocking; untouched when the call fails (it raises)"""
-        assert x.dtype == np.float32 and y.dtype == np.float32 and x.size == y.size and x.flags.c_contiguous and y.flags.c_contiguous
-        self._check(self._L.mdcu_undistort_points_host(int(device), C.byref(self.model), _np_ptr(x), _np_ptr(y), x.size))
+        self._host_call("undistort_points_host", x, y, device)
 
     def inverse_remap_device(self, d_ux, d_uy, d_outside, stream=0):
         """the model's in_w x in_h inverse tables into device arrays, *d_outside (an int32 on the device) = 1 if any entry is (-1, -1)"""
-        self._check(self._L.mdcu_inverse_remap_device(C.byref(self.model), d_ux, d_uy, d_outside, _stream(stream)))
+        self._device_call("inverse_remap_device", d_ux, d_uy, d_outside, stream)
 
 
 def huffman_lengths_device(d_hist, nsym, limit, d_lengths, stream=None):

@@ -1,7 +1,8 @@
 // codec_host.h -- the host-side helpers every device codec library has (libmdc_jenc.so, libmdc_jopt.so, libmdc_zipw.so, libmdc_pngw.so,
-// libmdc_pngw_rgb.so, libmdc_pnglz.so, libmdc_pngd.so, libmdc_pngdx.so): the thread's last error message, the guard that makes a
-// call run on its object's device, and the device resolution of the *_create calls.  Host only.  Each library is one translation
-// unit and includes this once (through its core header); everything is in its unnamed namespace, so each library has its own
+// libmdc_pngw_rgb.so, libmdc_pnglz.so, libmdc_pngd.so, libmdc_pngdx.so) and the two lens point libraries (libmdc_lens.so,
+// libmdc_lensinv.so) have: the thread's last error message, the guard that makes a call run on its object's device, and the device
+// resolution of the *_create calls.  Host only.  Each library is one translation unit and includes this once (through its core
+// header; the lens libraries through lens_points_shell.h); everything is in its unnamed namespace, so each library has its own
 // g_error and none exports any of it.
 //
 // The message buffer is 320 bytes in every library.  It was 320 in libmdc_zipw.so (whose messages carry errno's text) and 256 in

@@ -11,19 +11,13 @@
 #include "MdcBind.h"
 #include "host_device.h"
 #include "mdc_hip.h"
+#include "sibling_library.h"
 
 namespace mdc_host {
 
 bool DeviceLanes::load_multi() {
   if (mapi_.lib) return true;
-  Dl_info info;
-  std::string dir;
-  if (dladdr((void*)&open_device_context, &info) && info.dli_fname) {
-    dir = info.dli_fname;
-    const size_t sl = dir.rfind('/');
-    dir = sl == std::string::npos ? std::string() : dir.substr(0, sl + 1);
-  }
-  void* lib = dlopen((dir + "libmdc_multi.so").c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);  // RCCL keeps static state and helper threads: never unmapped again
+  void* lib = open_sibling_library("libmdc_multi.so");  // RCCL keeps static state and helper threads: never unmapped again
   if (!lib) return false;
   mapi_.create = (int (*)(const int*, int, void**))dlsym(lib, "mdc_multi_create");
   mapi_.destroy = (void (*)(void*))dlsym(lib, "mdc_multi_destroy");
@@ -39,19 +33,7 @@ bool DeviceLanes::load_multi() {
 }
 
 static const PngdApi* load_pngd(const char* env, const char* file, const char* prefix) {
-  std::string path;
-  if (const char* e = std::getenv(env)) {
-    path = e;
-  } else {
-    Dl_info info;
-    if (dladdr((void*)&open_device_context, &info) && info.dli_fname) {
-      path = info.dli_fname;
-      const size_t sl = path.rfind('/');
-      path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
-    }
-    path += file;
-  }
-  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);  // holds a HIP module: never unmapped again
+  void* lib = open_sibling_library(file, env);  // holds a HIP module: never unmapped again
   if (!lib) return 0;
   const std::string pre(prefix);
   PngdApi* a = new PngdApi;  // one per library and process, never freed

@@ -24,6 +24,7 @@
 #include "mdc_hip.h"
 #include "mdc_lens.h"
 #include "host_device.h"
+#include "sibling_library.h"
 #include "../fov_point_model.h"  // atanf_host_libm: the restatement the device runs, checked against THIS process's libm below
 #include "../lens_point_model.h"  // the RadTan / EquiDistant arithmetic and the crop rule, shared with libmdc_lens.so's kernels
 #include "mdc_lensinv.h"
@@ -309,38 +310,52 @@ void warp_points_lens(int kind, const mdc::LensModel& m, float* xs, float* ys, l
     for (long i = 0; i < n; i++) mdc::lens_distort_point<mdc::LENS_EQUIDISTANT>(m, xs[i], ys[i]);
 }
 
-// libmdc_lens.so's bulk call, loaded at run time the way device_lanes.cpp loads the PNG decoders: the file next to this library
-// (or the one MDC_LIB_LENS names), opened once per process and never closed (it holds a HIP module); 0 when it is not there.
-typedef int (*LensDistortHost)(int, const mdcn_model*, float*, float*, int64_t);
-struct LensApi {
-  LensDistortHost distort_points_host;
+// The bulk calls of libmdc_lens.so (distortCoordinates) and libmdc_lensinv.so (undistortCoordinates), loaded at run time the way
+// device_lanes.cpp loads the PNG decoders: the file next to this library (or the one `env` names), opened at a direction's first
+// bulk call, once per process, and never closed (it holds a HIP module).  mdcn_model and mdcu_model are the same 17 words, so one
+// function-pointer type serves both.
+static_assert(sizeof(mdcn_model) == 68 && sizeof(mdcu_model) == 68, "the two lens libraries take the same model words");
+struct LensLibrary {
+  const char* method;                         // UndistorterFOV's, for the messages
+  const char *file, *env;                     // the library, and the variable that names another file
+  const char *points_host_name, *last_error_name;
+  std::once_flag opened;
+  int (*points_host)(int, const void*, float*, float*, int64_t);  // 0 when the library is not there
   const char* (*last_error)();
+  bool said;
 };
+LensLibrary g_lens = {"distortCoordinates", "libmdc_lens.so", "MDC_LIB_LENS", "mdcn_distort_points_host", "mdcn_last_error"};
+LensLibrary g_lensinv = {"undistortCoordinates", "libmdc_lensinv.so", "MDC_LIB_LENSINV", "mdcu_undistort_points_host", "mdcu_last_error"};
 
-const LensApi* load_lens_api() {
-  std::string path;
-  if (const char* e = std::getenv("MDC_LIB_LENS")) {
-    path = e;
-  } else {
-    Dl_info info;
-    if (dladdr((void*)&mdc_host::open_device_context, &info) && info.dli_fname) {
-      path = info.dli_fname;
-      const size_t sl = path.rfind('/');
-      path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
-    }
-    path += "libmdc_lens.so";
-  }
-  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);
-  if (!lib) return 0;
-  static LensApi api;
-  api.distort_points_host = (LensDistortHost)dlsym(lib, "mdcn_distort_points_host");
-  api.last_error = (const char* (*)())dlsym(lib, "mdcn_last_error");
-  return api.distort_points_host && api.last_error ? &api : 0;
+bool lens_library_there(LensLibrary& l) {
+  std::call_once(l.opened, [&l] {
+    void* lib = mdc_host::open_sibling_library(l.file, l.env);
+    if (!lib) return;
+    l.last_error = (const char* (*)())dlsym(lib, l.last_error_name);
+    if (l.last_error) l.points_host = (int (*)(int, const void*, float*, float*, int64_t))dlsym(lib, l.points_host_name);
+  });
+  return l.points_host != 0;
 }
 
-const LensApi* lens_api() {
-  static const LensApi* api = load_lens_api();
-  return api;
+// A bulk call's way to the device: n points at or past the threshold (0 = never), `guard` (if any) agreeing, the library and a GPU
+// context there.  true: the device has written the n points.  false: the caller's host loop does the work -- the bits are the same
+// either way (one header, no FMA on either side) --, and where the library or the GPU is missing this says so once per direction.
+bool bulk_points_on_device(LensLibrary& l, long gpu_min, bool (*guard)(), mdc_ctx* gpu, const void* model, float* x, float* y, int n) {
+  if (!(gpu_min > 0 && n >= gpu_min && (!guard || guard()))) return false;
+  const bool there = lens_library_there(l);
+  mdc_info info;
+  if (there && gpu && mdc_get_info(gpu, &info) == MDC_OK) {
+    if (l.points_host(info.device, model, x, y, n) == MDCN_OK) return true;  // == MDCU_OK
+    // the call leaves the coordinates untouched when it fails (they are copied back last): say so and do the work on the host
+    std::fprintf(stderr, "UndistorterFOV::%s: the GPU call failed (%s); computing %d points on the host\n", l.method, l.last_error(), n);
+  } else {
+    if (!l.said && there) std::fprintf(stderr, "UndistorterFOV::%s: no GPU context; bulk calls are computed on the host (same results)\n", l.method);
+    if (!l.said && !there)
+      std::fprintf(stderr, "UndistorterFOV::%s: %s could not be loaded (%s names another file); bulk calls are computed on the host (same results)\n", l.method,
+                   l.file, l.env);
+    l.said = true;
+  }
+  return false;
 }
 
 // The device's atanf is a restatement of ONE libm's algorithm (glibc's fdlibm atanf).  A process linked against another libm
@@ -528,29 +543,16 @@ void UndistorterFOV::distortCoordinates(float* in_x, float* in_y, int n) {
   }();
   const LensState* const ls = find_lens_state(this);
   if (ls) {
-    // RadTan / EquiDistant: the same threshold; the bulk call is libmdc_lens.so's, loaded at run time.  Where the library or the GPU
-    // is missing the host loop does the work and says so once -- the bits are the same either way (one header, no FMA on either side).
+    // RadTan / EquiDistant: the same threshold; the bulk call is libmdc_lens.so's
     const mdc::LensModel lm = lens_model_of(ls->cam, ls->k, calib_out_, out_w_, out_h_);
-    if (gpu_min > 0 && n >= gpu_min && (ls->kind != mdc::LENS_EQUIDISTANT || libm_is_the_restated_one())) {
-      const LensApi* api = lens_api();
-      mdc_info info;
-      if (api && gpu_ && mdc_get_info(gpu_, &info) == MDC_OK) {
-        mdcn_model m;
-        m.kind = ls->kind;
-        m.fx = lm.fx, m.fy = lm.fy, m.cx = lm.cx, m.cy = lm.cy;
-        for (int i = 0; i < 4; i++) m.k[i] = lm.k[i];
-        m.in_w = in_w_, m.in_h = in_h_;
-        m.ofx = lm.ofx, m.ofy = lm.ofy, m.ocx = lm.ocx, m.ocy = lm.ocy;
-        m.out_w = out_w_, m.out_h = out_h_;
-        if (api->distort_points_host(info.device, &m, in_x, in_y, n) == MDCN_OK) return;
-        std::fprintf(stderr, "UndistorterFOV::distortCoordinates: the GPU call failed (%s); computing %d points on the host\n", api->last_error(), n);
-      } else {
-        static bool said = false;
-        if (!said) std::fprintf(stderr, "UndistorterFOV::distortCoordinates: %s; bulk calls are computed on the host (same results)\n",
-                                api ? "no GPU context" : "libmdc_lens.so could not be loaded (MDC_LIB_LENS names another file)");
-        said = true;
-      }
-    }
+    mdcn_model m;
+    m.kind = ls->kind;
+    m.fx = lm.fx, m.fy = lm.fy, m.cx = lm.cx, m.cy = lm.cy;
+    for (int i = 0; i < 4; i++) m.k[i] = lm.k[i];
+    m.in_w = in_w_, m.in_h = in_h_;
+    m.ofx = lm.ofx, m.ofy = lm.ofy, m.ocx = lm.ocx, m.ocy = lm.ocy;
+    m.out_w = out_w_, m.out_h = out_h_;
+    if (bulk_points_on_device(g_lens, gpu_min, ls->kind == mdc::LENS_EQUIDISTANT ? &libm_is_the_restated_one : 0, gpu_, &m, in_x, in_y, n)) return;
     warp_points_lens(ls->kind, lm, in_x, in_y, n);
     return;
   }
@@ -582,40 +584,6 @@ void unwarp_points(int kind, const mdc::LensInverseModel& m, float* xs, float* y
     for (long i = 0; i < n; i++) mdc::lens_undistort_point<mdc::LENSINV_EQUIDISTANT>(m, xs[i], ys[i]);
   else
     for (long i = 0; i < n; i++) mdc::lens_undistort_point<mdc::LENSINV_FOV>(m, xs[i], ys[i]);
-}
-
-// libmdc_lensinv.so's bulk call, loaded the way libmdc_lens.so's is: the file next to this library (or the one MDC_LIB_LENSINV
-// names), opened once per process and never closed; 0 when it is not there.
-typedef int (*LensUndistortHost)(int, const mdcu_model*, float*, float*, int64_t);
-struct LensInvApi {
-  LensUndistortHost undistort_points_host;
-  const char* (*last_error)();
-};
-
-const LensInvApi* load_lensinv_api() {
-  std::string path;
-  if (const char* e = std::getenv("MDC_LIB_LENSINV")) {
-    path = e;
-  } else {
-    Dl_info info;
-    if (dladdr((void*)&mdc_host::open_device_context, &info) && info.dli_fname) {
-      path = info.dli_fname;
-      const size_t sl = path.rfind('/');
-      path = sl == std::string::npos ? std::string() : path.substr(0, sl + 1);
-    }
-    path += "libmdc_lensinv.so";
-  }
-  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL | RTLD_NODELETE);
-  if (!lib) return 0;
-  static LensInvApi api;
-  api.undistort_points_host = (LensUndistortHost)dlsym(lib, "mdcu_undistort_points_host");
-  api.last_error = (const char* (*)())dlsym(lib, "mdcu_last_error");
-  return api.undistort_points_host && api.last_error ? &api : 0;
-}
-
-const LensInvApi* lensinv_api() {
-  static const LensInvApi* api = load_lensinv_api();
-  return api;
 }
 
 }  // namespace
@@ -656,20 +624,7 @@ void UndistorterFOV::undistortCoordinates(float* x, float* y, int n) {
   m.in_w = in_w_, m.in_h = in_h_;
   m.ofx = lm.ofx, m.ofy = lm.ofy, m.ocx = lm.ocx, m.ocy = lm.ocy;
   m.out_w = out_w_, m.out_h = out_h_;
-  if (gpu_min > 0 && n >= gpu_min) {
-    const LensInvApi* api = lensinv_api();
-    mdc_info info;
-    if (api && gpu_ && mdc_get_info(gpu_, &info) == MDC_OK) {
-      if (api->undistort_points_host(info.device, &m, x, y, n) == MDCU_OK) return;
-      // the call leaves the coordinates untouched when it fails (they are copied back last): say so and do the work here
-      std::fprintf(stderr, "UndistorterFOV::undistortCoordinates: the GPU call failed (%s); computing %d points on the host\n", api->last_error(), n);
-    } else {
-      static bool said = false;
-      if (!said) std::fprintf(stderr, "UndistorterFOV::undistortCoordinates: %s; bulk calls are computed on the host (same results)\n",
-                              api ? "no GPU context" : "libmdc_lensinv.so could not be loaded (MDC_LIB_LENSINV names another file)");
-      said = true;
-    }
-  }
+  if (bulk_points_on_device(g_lensinv, gpu_min, 0, gpu_, &m, x, y, n)) return;
   unwarp_points(m.kind, lm, x, y, n);
 }
 
