@@ -1,9 +1,12 @@
 // Internal to libmdc_hip.so: the context behind the opaque mdc_ctx of include/mdc_hip.h and what the translation units
 // of the C ABI share.  Not installed.
-//   mdc_capi.hip        lifetime, options, tables, the *_device entry points, tuning, table blobs; enqueue_process
+//   mdc_capi.hip        last error, lifetime, options and info, the calibration tables and their blob, mdc_synchronize
 //   mdc_plan.hip        tile / strip plans of the remap kernels (host side)
+//   mdc_launch.hip      the fused pass over device frames: which kernel runs (enqueue_process), describe_launch, tuning
+//   mdc_pyramid.hip     box pyramid and gradient images of device frames (gradient kernel, enqueue_pyramid_gradients)
 //   mdc_host_calls.hip  the synchronous host-pointer entry points (unMapImage / undistort<T> / getImage semantics)
 //   mdc_pipeline.hip    the pipelined many-frame host calls (raw frames, JPEG coefficient records, JPEG streams)
+//   mdc_placement.hip, mdc_jpeg.hip, mdc_vcal.hip, mdc_rcal.hip   a domain each: kernels, launchers, entry points
 #pragma once
 #include "../../include/mdc_hip.h"
 #include "mdc_internal.h"
@@ -197,19 +200,42 @@ struct DeviceGuard {
     return fail((c_), MDC_ERR_HIP, "unexpected exception");                              \
   }
 
+// a NULL context: no device (the only way to have none), or a caller's mistake -- what the calibration tools' calls return for it
+inline int no_ctx() { return mdc_device_count() > 0 ? MDC_ERR_ARG : MDC_ERR_NO_DEVICE; }
+
+// mdc_fov_model -> pixel-unit lens model, operation for operation as src/FOVUndistorter.cpp:289-301
+// (float products, `- 0.5` in double for the input camera, `- 0.5f`-equivalent narrowing for the output one,
+// double tan narrowed to float -- see DESIGN.md section 2).
+inline DistortModel distort_model(const mdc_fov_model* f) {
+  return make_distort_model(f->in_calib, f->in_w, f->in_h, f->out_calib, f->out_w, f->out_h);
+}
+
+// the frame size of a call: the rectified output, else the photometric tables' size, else the remap's input size (0: unknown)
+struct FrameSize {
+  int w, h;
+};
+inline FrameSize frame_size(const mdc_ctx* c, bool rectified) {
+  if (rectified) return {c->out_w, c->out_h};
+  return {c->in_w > 0 ? c->in_w : c->rm_in_w, c->in_h > 0 ? c->in_h : c->rm_in_h};
+}
+
 // ---- mdc_capi.hip ------------------------------------------------------------------------------------------------
 void normalise(const mdc_ctx* c, unsigned flags, bool& g, bool& v, bool& o);  // src/PhotometricUndistorter.cpp:173-189
 const float* lut_for(const mdc_ctx* c, bool g, bool o);
-int frames_per_block(const mdc_ctx* c, int64_t nframes, int blocks_per_group, int target_wgs = 4800);
-TilePlan tile_plan(const mdc_ctx* c, int which);
-RemapArgs remap_args(const mdc_ctx* c, const float* lut, const float* vinv);
+
+// ---- mdc_launch.hip ----------------------------------------------------------------------------------------------
 // the fused pass (or unMapImage alone) over device frames, on stream s; pyr: levels 1..3 wanted (-> *pyr_done: written by this launch)
 int enqueue_process(mdc_ctx* c, const uint8_t* d_in, float* d_out, int64_t nframes, unsigned flags, hipStream_t s, float* const* pyr = nullptr,
                     bool* pyr_done = nullptr);
+int enqueue_undistort_f32(mdc_ctx* c, const float* d_in, float* d_out, int64_t nframes, hipStream_t s);
+// the strip path's chunked launches, as mdc_get_info reports them
+int64_t prefetch_box_bytes(const mdc_ctx* c);
+int prefetch_streams(const mdc_ctx* c);
+int64_t prefetch_chunk_frames(const mdc_ctx* c, bool pyr = true);
+
+// ---- mdc_pyramid.hip ---------------------------------------------------------------------------------------------
 int enqueue_pyramid_gradients(mdc_ctx* c, const uint8_t* d_in, float* d_base, int levels, float* const* d_levels, float* const* d_dI,
                               float* const* d_abs_squared_grad, int64_t nframes, unsigned flags, int chunk_frames, hipStream_t s);
-int enqueue_undistort_f32(mdc_ctx* c, const float* d_in, float* d_out, int64_t nframes, hipStream_t s);
-DistortModel distort_model(const mdc_fov_model* f);
 
 // ---- mdc_plan.hip ------------------------------------------------------------------------------------------------
 int plan_tiles(mdc_ctx* c);  // (re)plans both source types and the strip kernel from the context's remap + options

@@ -1,5 +1,6 @@
-// Internal interface between the C-ABI layer (mdc_capi.hip, mdc_plan.hip, mdc_host_calls.hip, mdc_pipeline.hip) and the gfx950
-// kernels (mdc_kernels.hip).  Not installed; see include/mdc_hip.h for the ABI.
+// Internal interface between the host side of the C ABI (file map: mdc_ctx.h) and the gfx950 kernels that other units than their
+// own launch: the frame kernels (mdc_kernels.hip) and the JPEG decoder (mdc_jpeg.hip).  The domains whose kernels only their own
+// entry points launch (mdc_vcal.hip, mdc_rcal.hip, mdc_pyramid.hip) declare nothing here.  Not installed; the ABI: include/mdc_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -124,42 +125,6 @@ hipError_t launch_pyramid_level(const float* d_src, float* d_dst, int w, int h, 
 // (x, y) rectified pixel -> raw pixel, in place (UndistorterFOV::distortCoordinates).
 hipError_t launch_distort_points(float* d_x, float* d_y, int64_t n, const DistortModel& m, hipStream_t s);
 
-// vignetteCalib solver half-iterations (src/main_vignetteCalib.cpp:400-448, :455-527); d_er = {E, R}
-hipError_t launch_vcal_plane_step(const float* d_images, const float* d_p2x, const float* d_p2y, int n, int wI, int hI, int np,
-                                  float* d_plane_color, const float* d_vig, int oth2, float* d_ff, float* d_fc, double* d_er,
-                                  hipStream_t s);
-hipError_t launch_vcal_vignette_step(const float* d_images, const float* d_p2x, const float* d_p2y, int n, int wI, int hI, int np,
-                                     const float* d_plane_color, float* d_vig, int oth2, float* d_tt, float* d_ct, double* d_er,
-                                     unsigned* d_max_bits, hipStream_t s);
-
-// The vignette half-iteration as an ordered gather over a prebuilt per-pixel contribution index (mdc_vcal.hip):
-// bit-identical to the reference's sequential scatter, no atomics.
-struct VcalIndex;
-hipError_t vcal_index_build(const float* d_images, const float* d_p2x, const float* d_p2y, int n, int wI, int hI, int np,
-                            hipStream_t s, VcalIndex** out);
-void vcal_index_free(VcalIndex* ix);
-long long vcal_index_bytes(const VcalIndex* ix);
-long long vcal_index_entries(const VcalIndex* ix);
-hipError_t launch_vcal_vignette_step_indexed(const VcalIndex* ix, const float* d_plane_color, float* d_vig, int oth2, float* d_tt,
-                                             float* d_ct, double* d_er, unsigned* d_max_bits, hipStream_t s);
-
-// vignetteCalib: image = meanExposure * image / exposure_time[image] (:286-291), in place
-hipError_t launch_vcal_scale_images(float* d_images, int n, int64_t npix, float mean_exposure, const float* d_exposure, hipStream_t s);
-// vignetteCalib: gradient mask of n stacked w x h images, in place (:293-301)
-hipError_t launch_vcal_gradient_mask(float* d_images, int n, int wI, int hI, int max_abs_grad, hipStream_t s);
-// vignetteCalib: NaN coordinates for plane points outside the image (:345-357)
-hipError_t launch_vcal_mask_coords(float* d_x, float* d_y, int64_t n, int wI, int hI, hipStream_t s);
-// vignetteCalib: plane -> image coordinates of n frames (:230-258, :284, :345-357); d_corners (n x 8) -> d_hk (n x 9) first when
-// given; m == nullptr: the projection only
-hipError_t launch_vcal_plane_coords(const float* d_corners, float* d_hk, int n, int gw, int gh, float facw, float fach,
-                                    const DistortModel* m, int wI, int hI, float* d_p2x, float* d_p2y, hipStream_t s);
-// vignetteCalib's output smoothing (:541-566): four NaN-aware 3 x 3 mean passes; d_tt = result, d_ct = scratch
-hipError_t launch_vcal_smooth(const float* d_vig, int wI, int hI, float* d_tt, float* d_ct, hipStream_t s);
-// vignetteCalib's result images: displayImage's colour picture of the plane (:72-94; range_host = vmin, vmax) and the 16-bit
-// quantisation of vignette.png / vignetteSmoothed.png (:568-583); both synchronise `s`
-hipError_t launch_vcal_plot_plane(const float* d_plane, long long n, uint8_t* d_rgb, float* range_host, hipStream_t s);
-hipError_t launch_vcal_vignette_u16(const float* d_vignette, int64_t n, uint16_t* d_out, hipStream_t s);
-
 // JPEG ingest, device half: coefficient records (per frame: 64 x u16 luma quantisation table, then blocks_rows x blocks_w blocks
 // of 64 quantised int16 coefficients, natural order; record_bytes apart) -> 8-bit frames (nframes * w * h), libjpeg's islow
 // inverse DCT (mdc_jpeg.hip)
@@ -175,11 +140,5 @@ size_t jpeg_huffman_scratch_bytes(int64_t nframes);
 int jpeg_huffman_segments(int64_t nframes);
 hipError_t launch_jpeg_idct(const void* d_records, int64_t record_bytes, uint8_t* d_frames, int w, int h, int blocks_w, int blocks_rows,
                             int64_t nframes, hipStream_t s);
-
-// DSO hand-off of one pyramid level: (I, dx, dy) triples + absSquaredGrad (see mdc_vcal.hip)
-hipError_t launch_gradients(const float* d_level, float* d_dI, float* d_abs2, int w, int h, int64_t nframes, hipStream_t s);
-// ... of up to four levels in one launch
-hipError_t launch_gradients_levels(int n_levels, const float* const* d_src, float* const* d_dI, float* const* d_abs2, const int* w,
-                                   const int* h, int64_t nframes, hipStream_t s);
 
 }  // namespace mdc

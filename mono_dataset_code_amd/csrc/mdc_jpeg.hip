@@ -9,10 +9,7 @@
 // two 1-D passes run on a column / a row per thread with the block turned through LDS in between, every thread stores the eight
 // samples of its row.  In the reader the stage is bound by the PCIe transfer of the coefficients (2 bytes per pixel), which is what
 // it trades for the host's IDCT time; with the coefficients made on the device (Huffman kernels below) it is bound by HBM.
-#include "../../include/mdc_hip.h"
-#include "mdc_internal.h"
-
-#include <algorithm>
+#include "mdc_ctx.h"
 
 namespace mdc {
 namespace {
@@ -1092,3 +1089,39 @@ hipError_t launch_jpeg_idct(const void* d_records, int64_t record_bytes, uint8_t
 }
 
 }  // namespace mdc
+
+using namespace mdc;
+
+extern "C" {
+
+int mdc_jpeg_huffman_batch_device(mdc_ctx* c, const void* d_streams, int64_t stream_stride, void* d_records, int64_t record_bytes, int w, int h,
+                                  int blocks_w, int blocks_rows, int64_t nframes, int* d_status, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_streams || !d_records || !d_status || nframes < 0 || w <= 0 || h <= 0) return fail(c, MDC_ERR_ARG, "mdc_jpeg_huffman_batch_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  // small batches spread a frame's stream over several workgroups, which talk through a scratch buffer: stream-ordered
+  // allocation (nothing is shared between concurrent calls)
+  void* scratch = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  if (jpeg_huffman_segments(nframes) > 1 && hipMallocAsync(&scratch, jpeg_huffman_scratch_bytes(nframes), s) != hipSuccess) {
+    (void)hipGetLastError();
+    scratch = nullptr;  // (no pool: one workgroup per frame, as for large batches)
+  }
+  const hipError_t e = launch_jpeg_huffman(d_streams, stream_stride, d_records, record_bytes, w, h, blocks_w, blocks_rows, nframes, d_status, s, 7u, scratch);
+  if (scratch) (void)hipFreeAsync(scratch, s);
+  MDC_HIP(c, e);
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_jpeg_idct_batch_device(mdc_ctx* c, const void* d_records, int64_t record_bytes, uint8_t* d_frames, int w, int h, int blocks_w,
+                               int blocks_rows, int64_t nframes, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_records || !d_frames || nframes < 0 || w <= 0 || h <= 0) return fail(c, MDC_ERR_ARG, "mdc_jpeg_idct_batch_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_jpeg_idct(d_records, record_bytes, d_frames, w, h, blocks_w, blocks_rows, nframes, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+}  // extern "C"

@@ -1425,7 +1425,7 @@ static hipError_t launch_strip_passes(const uint8_t* d_in, float* d_out, const R
   return hipErrorInvalidValue;
 }
 #if MDC_EXP_STRIP_FAKE_GRAD
-float* g_fake_grad_dI = nullptr;  // diagnosis plumbing: set per launch by enqueue_pyramid_gradients (mdc_capi.hip)
+float* g_fake_grad_dI = nullptr;  // diagnosis plumbing: set per launch by enqueue_pyramid_gradients (mdc_pyramid.hip)
 float* g_fake_grad_abs = nullptr;
 #endif
 hipError_t launch_remap_strip_u8(const uint8_t* d_in, float* d_out, const RemapArgs& a, const StripPlan& p, int64_t nframes, int fpb,

@@ -768,4 +768,52 @@ int mdc_free_placed_device(mdc_ctx* c, mdc_placed_buffers* b) {
   return MDC_OK;
 }
 
+// Which of the caller's candidate buffers does the pass run fastest on?  (include/mdc_hip.h)
+int mdc_tune_placement_device(mdc_ctx* c, const uint8_t* const* d_in, int n_in, float* const* d_out, int n_out, int64_t nframes, unsigned flags,
+                              void* stream, int* best_in, int* best_out, float* ms_out) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_in || !d_out || n_in < 1 || n_out < 1 || (int64_t)n_in * n_out > 256 || nframes <= 0 || !best_in || !best_out)
+    return fail(c, MDC_ERR_ARG, "mdc_tune_placement_device: bad argument");
+  for (int k = 0; k < n_in; k++)
+    if (!d_in[k]) return fail(c, MDC_ERR_ARG, "mdc_tune_placement_device: input candidate %d is NULL", k);
+  for (int k = 0; k < n_out; k++)
+    if (!d_out[k]) return fail(c, MDC_ERR_ARG, "mdc_tune_placement_device: output candidate %d is NULL", k);
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  hipEvent_t e0, e1;
+  MDC_HIP(c, hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    return fail(c, MDC_ERR_HIP, "hipEventCreate failed");
+  }
+  int rc = MDC_OK, bi = 0, bo = 0;
+  float best = 1e30f;
+  for (int i = 0; i < n_in && rc == MDC_OK; i++)
+    for (int j = 0; j < n_out && rc == MDC_OK; j++) {
+      float ms[5] = {0, 0, 0, 0, 0};
+      for (int k = 0; k < 7 && rc == MDC_OK; k++) {  // 2 warm-up launches, 5 timed
+        bool ok = k < 2 || hipEventRecord(e0, s) == hipSuccess;
+        if (ok) rc = enqueue_process(c, d_in[i], d_out[j], nframes, flags, s);
+        if (rc != MDC_OK) break;
+        if (k >= 2) ok = ok && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms[k - 2], e0, e1) == hipSuccess;
+        if (!ok) rc = fail(c, MDC_ERR_HIP, "mdc_tune_placement_device: timing a launch failed");
+      }
+      if (rc != MDC_OK) break;
+      std::sort(ms, ms + 5);
+      if (ms_out) ms_out[(size_t)i * n_out + j] = ms[2];
+      if (ms[2] < best) {
+        best = ms[2];
+        bi = i;
+        bo = j;
+      }
+    }
+  (void)hipStreamSynchronize(s);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  *best_in = bi;
+  *best_out = bo;
+  return rc;
+} MDC_CATCH(c)
+
 }  // extern "C"

@@ -794,9 +794,6 @@ struct mdc_rcal_index {
 
 namespace {
 
-// a NULL context: no device (the only way to have none), or a caller's mistake
-int no_ctx() { return mdc_device_count() > 0 ? MDC_ERR_ARG : MDC_ERR_NO_DEVICE; }
-
 bool stack_ok(const void* d_images, const double* d_t, int n, int w, int h) {
   return d_images && d_t && n >= 1 && w >= 1 && h >= 1 && (long long)w * h < (1ll << 31) && (long long)n * w * h < (1ll << 46);
 }

@@ -1,4 +1,5 @@
-// gfx950 kernels for the vignetteCalib solver's accumulate loops (reference src/main_vignetteCalib.cpp:395-527):
+// gfx950 kernels, their launchers and the C entry points (mdc_vcal_*) of the vignetteCalib solver's accumulate loops (reference
+// src/main_vignetteCalib.cpp:395-527):
 // the alternating least-squares iteration that estimates the calibration plane's colour (one value per plane
 // point, gw*gh = 10^6 of them) and the per-pixel vignette factor from n images (up to ~1000) of the plane.
 // Per half-iteration the reference makes n*gw*gh bilinear gathers from the image stack and from the current
@@ -13,9 +14,7 @@
 //                   relative (tests/test_vcal.py: 1e-5).  Inverted into an ordered gather over a prebuilt index
 //                   (VcalIndex, vcal_vignette_gather_kernel) it is BIT-IDENTICAL and has no atomics on the data path;
 //   E (printed only, :449,:523): double sums in tree order instead of sequential order; R is an exact count.
-#include <vector>
-
-#include "mdc_internal.h"
+#include "mdc_ctx.h"
 #include "minmax_first.h"
 
 namespace mdc {
@@ -527,94 +526,6 @@ __global__ __launch_bounds__(256) void vcal_smooth_pass_kernel(const float* __re
   dst[idx] = num > 0 ? sum / num : own;  // :563
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// DSO hand-off (NOT in the reference -- DSO's FrameHessian::makeImages, definition in
-// DESIGN.md section 5.5): for one pyramid level, per pixel the triple (I, dx, dy) with central differences
-// dx = 0.5f*(I[idx+1] - I[idx-1]), dy = 0.5f*(I[idx+w] - I[idx-w]) over the LINEAR index range [w, w*(h-1)) -- rows
-// 1 .. h-2, all columns, so the first and last column difference across the row boundary exactly as DSO's loop
-// does --, non-finite differences replaced by 0, and absSquaredGrad = dx*dx + dy*dy.  First and last row: 0.
-// A wave handles 64 consecutive columns of kGradRows rows: all of its loads (rows y0-1 .. y0+R of the column, the left and
-// right neighbours of the R rows) are issued before the first result is needed -- the first version (one pixel per thread, one
-// 256-pixel workgroup per 4 KB of output) ran at the latency of its five loads, 3.5 TB/s of output; per row the wave's 192
-// floats (I, dx, dy interleaved) leave as three wave-contiguous dword stores through a wave-private LDS transpose instead
-// of three stores at a 12-byte stride.  Up to four pyramid levels of a chunk of frames in ONE launch
-// (mdc_process_pyramid_gradients_batch_device): a workgroup finds its level from the first-block table.
-// ---------------------------------------------------------------------------------------------------------
-constexpr int kGradRows = MDC_EXP_GRAD_ROWS, kGradThreads = 128;
-struct GradLevels {
-  const float* src[4];
-  float* dI[4];
-  float* abs2[4];
-  int w[4], h[4];
-  unsigned bx[4], bands[4];  // workgroups per row band (128 columns each), row bands (kGradRows rows each)
-  unsigned first_block[5];   // blocks [first_block[l], first_block[l+1]) belong to level l
-  int n;
-};
-__global__ __launch_bounds__(kGradThreads) void gradients_levels_kernel(GradLevels g) {
-  constexpr int R = kGradRows;
-  __shared__ float s_t[kGradThreads / 64][2][192];
-  int l = 0;
-#pragma unroll
-  for (int k = 1; k < 4; k++)
-    if (k < g.n && blockIdx.x >= g.first_block[k]) l = k;
-  const int w = g.w[l], h = g.h[l];
-  const unsigned b = blockIdx.x - g.first_block[l], per_frame = g.bx[l] * g.bands[l];
-  const unsigned f = b / per_frame, rb = b - f * per_frame, band = rb / g.bx[l], bx = rb - band * g.bx[l];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x0 = (int)bx * kGradThreads + wave * 64;  // first column of this wave
-  const int nvalid = min(64, w - x0);                  // wave-uniform
-  if (nvalid <= 0) return;
-  const int x = min(x0 + lane, w - 1);  // lanes past the row end repeat its last column (loads stay in bounds; nothing stored)
-  const int y0 = (int)band * R;
-  const int npx = w * h;
-  const float* p = g.src[l] + (long long)f * npx;
-  float c[R + 2], lf[R], rt[R];
-#ifdef MDC_EXP_GRAD_FAKE_READ  // diagnosis (wrong results): every read of the levels comes from the frame's first 16 KB -- what do these reads cost?
-#define MDC_GRAD_IDX(i) ((i) & 4095)
-#else
-#define MDC_GRAD_IDX(i) (i)
-#endif
-#pragma unroll
-  for (int r = -1; r <= R; r++) c[r + 1] = p[MDC_GRAD_IDX(min(max(y0 + r, 0), h - 1) * w + x)];
-  // left / right neighbours (linear index +-1): the neighbouring lanes' centre values; only the wave's first lane and its last valid
-  // one load theirs (one instruction with two active lanes per row instead of two unaligned row loads)
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int idx = min(y0 + r, h - 1) * w + x;
-    float le = 0.f, re = 0.f;
-    if (lane == 0) le = p[MDC_GRAD_IDX(max(idx - 1, 0))];
-    if (lane == nvalid - 1) re = p[MDC_GRAD_IDX(min(idx + 1, npx - 1))];
-    const float up = __shfl_up(c[r + 1], 1), dn = __shfl_down(c[r + 1], 1);
-    lf[r] = lane == 0 ? le : up;
-    rt[r] = lane == nvalid - 1 ? re : dn;
-  }
-#undef MDC_GRAD_IDX
-  float* dI = g.dI[l] + ((long long)f * npx + (long long)y0 * w + x0) * 3;
-  float* abs2 = g.abs2[l] + (long long)f * npx + (long long)y0 * w + x0;
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int y = y0 + r;
-    if (y >= h) break;  // wave-uniform
-    float dx = 0.f, dy = 0.f;
-    if (y >= 1 && y <= h - 2) {  // the linear index range [w, w*(h-1))
-      dx = 0.5f * (rt[r] - lf[r]);
-      dy = 0.5f * (c[r + 2] - c[r]);
-      if (!isfinite(dx)) dx = 0.f;
-      if (!isfinite(dy)) dy = 0.f;
-    }
-    if (lane < nvalid) __builtin_nontemporal_store(dx * dx + dy * dy, abs2 + (long long)r * w + lane);
-    float* t = s_t[wave][r & 1];
-    t[3 * lane + 0] = c[r + 1];
-    t[3 * lane + 1] = dx;
-    t[3 * lane + 2] = dy;
-    __builtin_amdgcn_wave_barrier();  // wave-private transpose: a wave's LDS operations execute in order
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-      if (k * 64 + lane < 3 * nvalid) __builtin_nontemporal_store(t[k * 64 + lane], dI + (long long)r * w * 3 + k * 64 + lane);
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
 inline int blocks(long long n) { return (int)((n + 255) / 256); }
 
 // ---- the result images: displayImage (:72-94) and the 16-bit vignette files (:568-583)
@@ -664,8 +575,8 @@ __global__ __launch_bounds__(256) void vcal_vignette_u16_kernel(const float* __r
   }
 }
 
-}  // namespace
-
+// vignetteCalib's result images: displayImage's colour picture of the plane (:72-94; range_host = vmin, vmax) and the 16-bit
+// quantisation of vignette.png / vignetteSmoothed.png (:568-583); both synchronise `s`
 hipError_t launch_vcal_plot_plane(const float* d_plane, long long n, uint8_t* d_rgb, float* range_host, hipStream_t s) {
   const int nparts = (int)std::min<long long>(kVcalPlotBlocks, blocks(n));
   MinMaxFirst<float>* d_part = nullptr;
@@ -694,33 +605,7 @@ hipError_t launch_vcal_vignette_u16(const float* d_vignette, int64_t n, uint16_t
   return e != hipSuccess ? e : e2;
 }
 
-hipError_t launch_gradients_levels(int n_levels, const float* const* d_src, float* const* d_dI, float* const* d_abs2, const int* w,
-                                   const int* h, int64_t nframes, hipStream_t s) {
-  if (n_levels <= 0 || nframes <= 0) return hipSuccess;
-  if (n_levels > 4) return hipErrorInvalidValue;
-  GradLevels g;
-  uint64_t nb = 0;
-  for (int l = 0; l < 4; l++) {
-    const bool on = l < n_levels && w[l] > 0 && h[l] > 0;
-    g.src[l] = on ? d_src[l] : nullptr;
-    g.dI[l] = on ? d_dI[l] : nullptr;
-    g.abs2[l] = on ? d_abs2[l] : nullptr;
-    g.w[l] = on ? w[l] : 1;
-    g.h[l] = on ? h[l] : 1;
-    g.bx[l] = (unsigned)((g.w[l] + kGradThreads - 1) / kGradThreads);
-    g.bands[l] = (unsigned)((g.h[l] + kGradRows - 1) / kGradRows);
-    g.first_block[l] = (unsigned)nb;
-    if (on) nb += (uint64_t)g.bx[l] * g.bands[l] * (uint64_t)nframes;
-    if ((int64_t)g.w[l] * g.h[l] >= (1ll << 30)) return hipErrorInvalidValue;  // 32-bit pixel indices inside a frame
-  }
-  if (nb >= (1ull << 31)) return hipErrorInvalidValue;  // callers split such batches (mdc_capi.hip)
-  g.first_block[4] = (unsigned)nb;
-  g.n = n_levels;
-  if (nb == 0) return hipSuccess;
-  gradients_levels_kernel<<<(unsigned)nb, kGradThreads, 0, s>>>(g);
-  return hipGetLastError();
-}
-
+// the solver's half-iterations (:400-448, :455-527); d_er = {E, R}
 hipError_t launch_vcal_plane_step(const float* d_images, const float* d_p2x, const float* d_p2y, int n, int wI, int hI, int np,
                                   float* d_plane_color, const float* d_vig, int oth2, float* d_ff, float* d_fc, double* d_er,
                                   hipStream_t s) {
@@ -859,6 +744,8 @@ hipError_t launch_vcal_mask_coords(float* d_x, float* d_y, int64_t n, int wI, in
   return hipGetLastError();
 }
 
+// plane -> image coordinates of n frames (:230-258, :284, :345-357); d_corners (n x 8) -> d_hk (n x 9) first when given;
+// m == nullptr: the projection only
 hipError_t launch_vcal_plane_coords(const float* d_corners, float* d_hk, int n, int gw, int gh, float facw, float fach,
                                     const DistortModel* m, int wI, int hI, float* d_p2x, float* d_p2y, hipStream_t s) {
   if (n <= 0) return hipSuccess;
@@ -882,20 +769,205 @@ hipError_t launch_vcal_smooth(const float* d_vig, int wI, int hI, float* d_tt, f
   return hipGetLastError();
 }
 
-hipError_t launch_gradients(const float* d_level, float* d_dI, float* d_abs2, int w, int h, int64_t nframes, hipStream_t s) {
-  if (w <= 0 || h <= 0) return hipSuccess;
-  // launches of at most 2^30 workgroups
-  const int64_t per_frame = (int64_t)((w + kGradThreads - 1) / kGradThreads) * ((h + kGradRows - 1) / kGradRows);
-  const int64_t step = std::max<int64_t>(1, (1ll << 30) / per_frame);
-  const int64_t npx = (int64_t)w * h;
-  for (int64_t f0 = 0; f0 < nframes; f0 += step) {
-    const float* src = d_level + f0 * npx;
-    float* dI = d_dI + f0 * npx * 3;
-    float* a2 = d_abs2 + f0 * npx;
-    hipError_t e = launch_gradients_levels(1, &src, &dI, &a2, &w, &h, std::min(step, nframes - f0), s);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+}  // namespace
+}  // namespace mdc
+
+using namespace mdc;
+
+struct mdc_vcal_index {
+  mdc::VcalIndex* ix;
+  int device;
+};
+
+extern "C" {
+
+int mdc_vcal_plane_step_device(mdc_ctx* c, const float* d_images, const float* d_p2x, const float* d_p2y, int n_images, int w, int h,
+                               int n_plane, float* d_plane_color, const float* d_vignette_factor, int oth2, float* d_ff,
+                               float* d_fc, double* d_er, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_images || !d_p2x || !d_p2y || !d_plane_color || !d_vignette_factor || !d_ff || !d_fc || !d_er || n_images < 0 || w < 2 ||
+      h < 2 || n_plane < 0 || (long long)w * h >= (1ll << 31))  // int pixel indices in the kernel
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_plane_step_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_plane_step(d_images, d_p2x, d_p2y, n_images, w, h, n_plane, d_plane_color, d_vignette_factor, oth2, d_ff,
+                                    d_fc, d_er, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_vignette_step_device(mdc_ctx* c, const float* d_images, const float* d_p2x, const float* d_p2y, int n_images, int w,
+                                  int h, int n_plane, const float* d_plane_color, float* d_vignette_factor, int oth2, float* d_tt,
+                                  float* d_ct, double* d_er, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_images || !d_p2x || !d_p2y || !d_plane_color || !d_vignette_factor || !d_tt || !d_ct || !d_er || n_images < 0 ||
+      n_images > 65535 || w < 2 || h < 2 || n_plane < 0 || (long long)w * h >= (1ll << 31))  // grid y = n_images; int pixel indices
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_vignette_step_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_vignette_step(d_images, d_p2x, d_p2y, n_images, w, h, n_plane, d_plane_color, d_vignette_factor, oth2,
+                                       d_tt, d_ct, d_er, c->d_vcal_max + (c->vcal_max_next++ % mdc_ctx::kVcalMaxWords), (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_index_create(mdc_ctx* c, const float* d_images, const float* d_p2x, const float* d_p2y, int n_images, int w, int h,
+                          int n_plane, void* stream, mdc_vcal_index** out) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!out) return fail(c, MDC_ERR_ARG, "mdc_vcal_index_create: out is NULL");
+  *out = nullptr;
+  if (!d_images || !d_p2x || !d_p2y || n_images < 0 || n_images > 65535 || w < 2 || h < 2 || n_plane < 0 || n_plane >= (1 << 30) ||
+      (long long)w * h >= (1ll << 31))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_index_create: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  mdc::VcalIndex* ix = nullptr;
+  MDC_HIP(c, mdc::vcal_index_build(d_images, d_p2x, d_p2y, n_images, w, h, n_plane, (hipStream_t)stream, &ix));
+  *out = new mdc_vcal_index{ix, c->device};
+  return MDC_OK;
+} MDC_CATCH(c)
+
+void mdc_vcal_index_destroy(mdc_vcal_index* index) {
+  if (!index) return;
+  DeviceGuard dg(index->device);
+  mdc::vcal_index_free(index->ix);
+  delete index;
 }
 
-}  // namespace mdc
+int64_t mdc_vcal_index_bytes(const mdc_vcal_index* index) { return index ? mdc::vcal_index_bytes(index->ix) : 0; }
+int64_t mdc_vcal_index_entries(const mdc_vcal_index* index) { return index ? mdc::vcal_index_entries(index->ix) : 0; }
+
+int mdc_vcal_vignette_step_indexed_device(mdc_ctx* c, const mdc_vcal_index* index, const float* d_plane_color,
+                                          float* d_vignette_factor, int oth2, float* d_tt, float* d_ct, double* d_er, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!index || !d_plane_color || !d_vignette_factor || !d_tt || !d_ct || !d_er)
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_vignette_step_indexed_device: bad argument");
+  if (index->device != c->device) return fail(c, MDC_ERR_ARG, "mdc_vcal_vignette_step_indexed_device: index built on another device");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, mdc::launch_vcal_vignette_step_indexed(index->ix, d_plane_color, d_vignette_factor, oth2, d_tt, d_ct, d_er,
+                                                    c->d_vcal_max + (c->vcal_max_next++ % mdc_ctx::kVcalMaxWords), (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_scale_images_device(mdc_ctx* c, float* d_images, int n_images, int64_t npix, float mean_exposure,
+                                 const float* d_exposure_times, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (n_images < 0 || n_images > 65535 || npix < 0 || (n_images > 0 && npix > 0 && (!d_images || !d_exposure_times)))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_scale_images_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_scale_images(d_images, n_images, npix, mean_exposure, d_exposure_times, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_gradient_mask_device(mdc_ctx* c, float* d_images, int n_images, int w, int h, int max_abs_grad, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (n_images < 0 || (n_images > 0 && !d_images) || w < 1 || h < 1 || (long long)w * h >= (1ll << 31) || max_abs_grad < 0)
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_gradient_mask_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_gradient_mask(d_images, n_images, w, h, max_abs_grad, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_mask_coords_device(mdc_ctx* c, float* d_x, float* d_y, int64_t n, int w, int h, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (n < 0 || (n > 0 && (!d_x || !d_y)) || w < 1 || h < 1) return fail(c, MDC_ERR_ARG, "mdc_vcal_mask_coords_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_mask_coords(d_x, d_y, n, w, h, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_plane_coords_device(mdc_ctx* c, const mdc_fov_model* model, const float* d_corners, float* d_hk, int n, int gw, int gh,
+                                 float facw, float fach, float* d_p2x, float* d_p2y, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (n < 0 || n > 65535 || gw < 1 || gh < 1 || (long long)gw * gh >= (1ll << 31) ||
+      (n > 0 && (!d_hk || !d_p2x || !d_p2y)) || (model && (model->in_w < 1 || model->in_h < 1)))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_plane_coords_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  DistortModel m;
+  if (model) m = distort_model(model);
+  MDC_HIP(c, launch_vcal_plane_coords(d_corners, d_hk, n, gw, gh, facw, fach, model ? &m : nullptr, model ? model->in_w : 0,
+                                      model ? model->in_h : 0, d_p2x, d_p2y, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_smooth_device(mdc_ctx* c, const float* d_vignette_factor, int w, int h, float* d_smoothed, float* d_scratch,
+                           void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_vignette_factor || !d_smoothed || !d_scratch || w < 1 || h < 1 || (long long)w * h >= (1ll << 31) ||
+      d_smoothed == d_scratch || d_vignette_factor == d_scratch)
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_smooth_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_smooth(d_vignette_factor, w, h, d_smoothed, d_scratch, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_plot_plane_device(mdc_ctx* c, const float* d_plane, int gw, int gh, uint8_t* d_rgb, float* range_host, void* stream) try {
+  if (!c) return no_ctx();
+  if (!d_plane || !d_rgb || !range_host || gw < 1 || gh < 1 || (long long)gw * gh >= (1ll << 31))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_plot_plane_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_plot_plane(d_plane, (long long)gw * gh, d_rgb, range_host, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_vignette_u16_device(mdc_ctx* c, const float* d_vignette, int64_t n, uint16_t* d_out, void* stream) try {
+  if (!c) return no_ctx();
+  if (n < 0 || (n > 0 && (!d_vignette || !d_out)) || ((uintptr_t)d_out & 1) || ((uintptr_t)d_vignette & 3))
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_vignette_u16_device: bad argument");
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  MDC_HIP(c, launch_vcal_vignette_u16(d_vignette, n, d_out, (hipStream_t)stream));
+  return MDC_OK;
+} MDC_CATCH(c)
+
+int mdc_vcal_solve_device(mdc_ctx* c, const float* d_images, const float* d_p2x, const float* d_p2y, int n_images, int w, int h,
+                          int n_plane, float* d_plane_color, float* d_vignette_factor, int max_iterations, int outlier_th,
+                          double* er_out, void* stream) try {
+  if (!c) return MDC_ERR_ARG;
+  if (!d_plane_color || !d_vignette_factor || max_iterations < 0 || outlier_th < 0 || outlier_th > 46340)
+    return fail(c, MDC_ERR_ARG, "mdc_vcal_solve_device: bad argument");
+  if (max_iterations == 0) return MDC_OK;
+  mdc_vcal_index* index = nullptr;
+  int rc = mdc_vcal_index_create(c, d_images, d_p2x, d_p2y, n_images, w, h, n_plane, stream, &index);
+  if (rc != MDC_OK) return rc;
+  ReadLock lk(c->mu);
+  DeviceGuard dg(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  float *d_ff = nullptr, *d_fc = nullptr, *d_tt = nullptr, *d_ct = nullptr;
+  double* d_er = nullptr;
+  const size_t plane_bytes = (size_t)std::max(n_plane, 1) * sizeof(float), img_bytes = (size_t)w * h * sizeof(float);
+  const size_t er_bytes = (size_t)max_iterations * 4 * sizeof(double);
+  auto done = [&](int code) {
+    (void)hipStreamSynchronize(s);
+    for (void* p : {(void*)d_ff, (void*)d_fc, (void*)d_tt, (void*)d_ct, (void*)d_er}) (void)hipFree(p);
+    mdc_vcal_index_destroy(index);
+    return code;
+  };
+#define MDC_SOLVE(call_)                                                  \
+  do {                                                                    \
+    hipError_t e_ = (call_);                                              \
+    if (e_ != hipSuccess) return done(fail(c, MDC_ERR_HIP, "%s: %s", #call_, hipGetErrorString(e_))); \
+  } while (0)
+  MDC_SOLVE(hipMalloc(&d_ff, plane_bytes));
+  MDC_SOLVE(hipMalloc(&d_fc, plane_bytes));
+  MDC_SOLVE(hipMalloc(&d_tt, img_bytes));
+  MDC_SOLVE(hipMalloc(&d_ct, img_bytes));
+  MDC_SOLVE(hipMalloc(&d_er, er_bytes));
+  for (int it = 0; it < max_iterations; it++) {
+    const int oth2 = it < max_iterations / 2 ? 10000 * 10000 : outlier_th * outlier_th;  // :397-398
+    MDC_SOLVE(launch_vcal_plane_step(d_images, d_p2x, d_p2y, n_images, w, h, n_plane, d_plane_color, d_vignette_factor, oth2, d_ff,
+                                     d_fc, d_er + 4 * it, s));
+    MDC_SOLVE(mdc::launch_vcal_vignette_step_indexed(index->ix, d_plane_color, d_vignette_factor, oth2, d_tt, d_ct, d_er + 4 * it + 2,
+                                                     c->d_vcal_max + (c->vcal_max_next++ % mdc_ctx::kVcalMaxWords), s));
+  }
+  if (er_out) MDC_SOLVE(hipMemcpyAsync(er_out, d_er, er_bytes, hipMemcpyDeviceToHost, s));
+#undef MDC_SOLVE
+  return done(MDC_OK);
+} MDC_CATCH(c)
+
+}  // extern "C"

@@ -15,7 +15,7 @@ def kernels():
     import isa_stats
 
     ks = []
-    for src in ("mdc_kernels.hip", "mdc_vcal.hip", "mdc_jpeg.hip"):
+    for src in ("mdc_kernels.hip", "mdc_vcal.hip", "mdc_jpeg.hip", "mdc_pyramid.hip"):
         ks += isa_stats.kernels(isa_stats.device_asm(src))
     assert len(ks) > 100
     return ks
